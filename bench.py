@@ -1,6 +1,6 @@
 """Headline benchmark: frames/s of the forward render path on synthetic random-Gaussian scenes.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3] [--dump-outputs DIR]
 
 A step = one `render_gaussians(..., backend="hip")` forward (project -> bin/sort -> rasterise)
 of the whole frame, inputs resident in HBM.  N=1 workload = BASELINE config 3's forward
@@ -17,6 +17,9 @@ After the timed loop the frame that was timed is VERIFIED: rendered once more th
 call and compared bit for bit with the per-stage path (project -> bin -> rasterise through the
 per-stage C entry points: gsplat-exact, fully sorted lists), and -- N=1 -- against the C oracle's
 frame under the test-suite's bar (tests/helpers.py check_image_strict).  A mismatch fails the run.
+
+`--dump-outputs DIR` writes, once the run is over, the image the last timed step returned (float32; an image over 64 MB
+as a fixed, seeded sample of its pixels): the inputs are seeded, so two builds can be compared output for output.
 
 `roofline` prices the dominant kernel (the tile rasteriser) with SURVEY.md 8(d)'s algorithmic
 bytes (40 B/intersection + 8 B/tile + 12 B/pixel) over its average duration measured with HIP
@@ -68,6 +71,7 @@ WORKLOADS = {
     "cfg5": (5_000_000, 3840, 2160, -4.0, False),
 }
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec
+DUMP_BYTES = 64_000_000  # --dump-outputs: at most this many bytes in all, .npy headers included
 
 
 def parse_args(argv=None):
@@ -84,6 +88,10 @@ def parse_args(argv=None):
                          "report config 5 (the config BASELINE names for 8 GPUs) under `extras`")
     ap.add_argument("--no-extras", action="store_true",
                     help="N>1: skip the config-5 leg; N=1: skip the moving-camera and forward+backward legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the image the last timed step returned to DIR/image.npy (float32, H x W x C); an image "
+                         "over %d MB is written as DIR/image_sample.npy instead: the pixels at a fixed, seeded "
+                         "sample of positions (rows of C)" % (DUMP_BYTES // 10**6))
     return ap.parse_args(argv)
 
 
@@ -95,6 +103,8 @@ def self_launch(args):
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+    if args.dump_outputs:   # the ranks run in ROOT: a relative DIR is the caller's
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     env.setdefault("OMP_NUM_THREADS", "4")
     proc = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, text=True, cwd=ROOT)
@@ -151,11 +161,14 @@ def main():
     mode = {"async": True}
 
     def barrier():
+        """-> the image of the last frame it drained (N > 1, frames in flight), else None."""
+        last = None
         if world > 1:
             while in_flight:
-                in_flight.pop(0).wait()
+                last = in_flight.pop(0).wait()
             dist.barrier()
         torch.cuda.synchronize()
+        return last
 
     def load(name):
         N, W, H, ell, fp16 = WORKLOADS[name]
@@ -308,10 +321,14 @@ def main():
     stamps = [0.0] * (args.steps + 1)
     t0 = stamps[0] = time.perf_counter()
     for k in range(args.steps):
-        step()
+        last_img = step()
         stamps[k + 1] = time.perf_counter()   # (the call returns once the frame's size record is in: one frame behind the GPU)
-    barrier()
+    drained = barrier()
     dt = time.perf_counter() - t0
+    # the image the last timed step delivered (N > 1 with frames in flight: the frame the closing barrier drained)
+    last_img = drained if drained is not None else last_img
+    if not args.dump_outputs:
+        last_img = None
     render_mod._STAGE_HOOK = None
     periods = sorted(b - a for a, b in zip(stamps[1:-1], stamps[2:]))   # (the first period holds the pipeline's fill)
     # where a short run's wall time goes: the first call (pipeline fill), the periods, the drain at the closing barrier
@@ -586,6 +603,8 @@ def main():
             "roofline": roofline, "cpu_baseline": cpu,
             "extras": (dict(extras or {}, **legs) or None),
         }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"image": last_img})
         print(json.dumps(out), flush=True)
         if not verified:
             print("[bench] VERIFICATION FAILED: the timed frame differs from the per-stage path / the oracle",
@@ -598,6 +617,24 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     sys.exit(rc)
+
+
+def dump_outputs(path, arrays):
+    """Write each output as path/<name>.npy in float32.  When they come to more than DUMP_BYTES in all, each is written
+    as path/<name>_sample.npy instead: its rows along the last axis (an image's pixels) at positions drawn from a fixed
+    seed, so that two runs of the same workload sample the same pixels."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES:
+            rows = a.reshape(-1, a.shape[-1])
+            keep = min(len(rows), (DUMP_BYTES // len(arrays) - 1024) // rows[0].nbytes)   # (1 KB: the header)
+            pick = np.sort(np.random.default_rng(0).choice(len(rows), keep, replace=False))
+            a, name = rows[pick], name + "_sample"
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        print(f"[bench] wrote {os.path.join(path, name + '.npy')} {a.shape}", file=sys.stderr, flush=True)
 
 
 def morton_leg(ms, _fused, g, cam, bg, ref_img, given_ms, frames=200):
