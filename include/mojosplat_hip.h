@@ -19,6 +19,8 @@
  *   ms_render_fwd                     the whole of render_gaussians' device work
  *                                     (mojosplat/render.py:63-101) in one call
  *   ms_render_bwd                     the backward of such a frame (no reference counterpart) in one call
+ *   ms_render_bwd_finish_densify,     3DGS densification statistics accumulated in a training backward
+ *   ms_densify_stats_update           (no reference counterpart)
  *   ms_render_fwd_batch               the same for C cameras: the camera dimension of the reference's
  *                                     kernels (kernels/projection.mojo:32-37) that its wrappers pin to 1
  *
@@ -270,6 +272,31 @@ int ms_render_bwd_finish(int64_t N, const float *means3d, const float *scales, i
                          const float *opacities, int CDIM, const float *viewmat, float fx, float fy, float cx, float cy,
                          int W, int H, float eps2d, const float *rows, float *v_means3d, float *v_scales, float *v_quats,
                          float *v_opacities, float *v_colors, void *stream);
+
+/* 3DGS densification statistics (adaptive density control: Kerbl et al. 2023; gsplat's default strategy), accumulated
+ * over the views of a training step into three caller-owned buffers f32[N] (non-null, 4-byte aligned, not zeroed by the
+ * library).  For every Gaussian i ALIVE in the view -- radii > 0 under the frame's own projection
+ * (ms_project_gaussians_fwd with the opacities, near_plane / far_plane, eps2d and radius_clip 0) -- with g = dL/dmeans2d
+ * of the view in pixels:
+ *   count[i]     += 1
+ *   grad2d[i]    += sqrt((g.x * W / 2)^2 + (g.y * H / 2)^2)          (the gradient in NDC units)
+ *   max_radii[i]  = max(max_radii[i], max(radius.x, radius.y) / max(W, H))
+ * A Gaussian alive but never blended counts, with a zero gradient; one that is not alive is left untouched.
+ *   ms_render_bwd_finish_densify: ms_render_bwd_finish (same arguments, same gradients bit for bit) that also updates the
+ *     statistics of the frame: the backward projection re-projects each Gaussian for the verdict and the radii (a lean
+ *     differentiable frame writes no radii) and takes g from the rows it is finishing anyway.  The rows must be the
+ *     whole frame's (one rank's band rows summed over the ranks are).
+ *   ms_densify_stats_update: the same update for a caller that already holds v_means2d f32[N,2] and the forward's
+ *     radii i32[N,2] (both 8-byte aligned) -- the per-stage path.
+ * One backward of a view calls either entry point once.  No reference counterpart (render.py:11). */
+int ms_render_bwd_finish_densify(int64_t N, const float *means3d, const float *scales, int scales_are_log,
+                                 const float *quats, const float *opacities, int CDIM, const float *viewmat, float fx,
+                                 float fy, float cx, float cy, int W, int H, float eps2d, const float *rows,
+                                 float *v_means3d, float *v_scales, float *v_quats, float *v_opacities, float *v_colors,
+                                 float near_plane, float far_plane, float *grad2d, float *count, float *max_radii,
+                                 void *stream);
+int ms_densify_stats_update(int64_t N, int W, int H, const int32_t *radii, const float *v_means2d, float *grad2d,
+                            float *count, float *max_radii, void *stream);
 
 /* Bins the clean-up pass of a finished ms_render_fwd frame had to redo (lazily sorted fronts that ran out with pixels
  * alive): host_counts i32[2] = {all redone bins, those redone for their depth cut-off}, copied asynchronously on `stream`

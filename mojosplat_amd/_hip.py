@@ -119,6 +119,11 @@ _SIGNATURES["ms_render_bwd_rows"] = (c_int, [c_int64, c_int, c_int, c_int, c_int
 _SIGNATURES["ms_render_bwd_finish"] = (c_int, [c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_float, c_float,
                                                c_float, c_float, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                c_void_p, c_void_p])
+_SIGNATURES["ms_render_bwd_finish_densify"] = (c_int, [c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_float,
+                                                       c_float, c_float, c_float, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                                       c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                                                       c_void_p])
+_SIGNATURES["ms_densify_stats_update"] = (c_int, [c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
 _SIGNATURES["ms_scene_block_bounds_bytes"] = (c_size_t, [c_int64, c_int])
 _SIGNATURES["ms_scene_prepare"] = (c_int, [c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p])
 _SIGNATURES["ms_render_band_begin"] = (c_int, [ctypes.POINTER(BandFrame), ctypes.POINTER(BandLane), c_void_p])

@@ -12,10 +12,12 @@ Binning is index work and carries no gradient.
 """
 import ctypes
 import os
+from typing import Optional
 
 import torch
 
 from . import _hip
+from .densify import DensifyStats
 from .binning import bin_gaussians_to_tiles_hip
 from .projection import EPS2D, project_gaussians_hip
 from .rasterization import rasterize_gaussians_hip
@@ -24,11 +26,12 @@ from .utils import Camera
 
 class _ProjectHip(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, means3d, scales, quats, opacities, camera):
+    def forward(ctx, means3d, scales, quats, opacities, camera, densify=None):
         means3d, scales, quats = _hip.f32c(means3d), _hip.f32c(scales), _hip.f32c(quats)
         out = project_gaussians_hip(means3d, scales, quats, opacities, camera)
         means2d, conics, depths, radii = out
         ctx.camera = camera
+        ctx.densify = densify   # (DensifyStats: updated by the first backward only)
         ctx.save_for_backward(means3d, scales, quats, radii)
         ctx.mark_non_differentiable(radii)
         return means2d, conics, depths, radii
@@ -53,7 +56,12 @@ class _ProjectHip(torch.autograd.Function):
                 cam.fy, cam.cx, cam.cy, cam.W, cam.H, EPS2D, _hip.ptr(radii), _hip.ptr(v_means2d),
                 _hip.ptr(v_conics), _hip.ptr(v_depths), _hip.ptr(v_means3d), _hip.ptr(v_scales),
                 _hip.ptr(v_quats), _hip.stream(dev)), "ms_project_gaussians_bwd")
-        return v_means3d, v_scales, v_quats, None, None
+            if ctx.densify is not None:
+                st, ctx.densify = ctx.densify, None
+                _hip.check(L.ms_densify_stats_update(N, cam.W, cam.H, _hip.ptr(radii), _hip.ptr(v_means2d), _hip.ptr(st.grad2d),
+                                                     _hip.ptr(st.count), _hip.ptr(st.max_radii), _hip.stream(dev)),
+                           "ms_densify_stats_update")
+        return v_means3d, v_scales, v_quats, None, None, None
 
 
 class _RasterizeHip(torch.autograd.Function):
@@ -108,7 +116,7 @@ class _RenderFusedHip(torch.autograd.Function):
     rasterise -- the inference path's forward -- with the frame's scratch kept alive for backward."""
 
     @staticmethod
-    def forward(ctx, means3d, scales, quats, opacities, colors, background, camera, tile_size):
+    def forward(ctx, means3d, scales, quats, opacities, colors, background, camera, tile_size, densify=None):
         from ._fused import WHOLE, _Frame
         from . import render as _render   # bench.py's in-situ stage timing hook (None otherwise)
         evs = _render._STAGE_HOOK() if _render._STAGE_HOOK is not None else None
@@ -136,6 +144,8 @@ class _RenderFusedHip(torch.autograd.Function):
             _render._settle(key, tile_size, _render.bin_rule(tile_size, M, info["on_grid"], camera.W, camera.H, grid_px=tile_size))
         ctx.empty = info["on_grid"] == 0
         ctx.camera, ctx.tile_size = camera, tile_size
+        # (DensifyStats of a lean frame: the first backward's finish updates them; an empty frame has nothing alive)
+        ctx.densify = densify if lean else None
         m3, sc, qu, op, col, bg = frame.keep[:6]
         if ctx.empty:
             ctx.save_for_backward(m3, sc, qu, op, col, bg)
@@ -157,7 +167,7 @@ class _RenderFusedHip(torch.autograd.Function):
         if ctx.empty:
             m3, sc, qu, op, col, bg = ctx.saved_tensors
             return (torch.zeros_like(m3), torch.zeros_like(sc), torch.zeros_like(qu), torch.zeros_like(op),
-                    torch.zeros_like(col), None if bg is None else torch.zeros_like(bg), None, None)
+                    torch.zeros_like(col), None if bg is None else torch.zeros_like(bg), None, None, None)
         m3, sc, qu, op, col, bg, alphas, last, img = ctx.saved_tensors
         ws, isect, host = ctx.scratch
         L = _hip.lib()
@@ -202,10 +212,18 @@ class _RenderFusedHip(torch.autograd.Function):
                     host[7] = int(host[7]) & ~32768
                 if bev:
                     bev[1].record()
-                _hip.check(L.ms_render_bwd_finish(N, _hip.ptr(m3), _hip.ptr(sc), 1, _hip.ptr(qu), _hip.ptr(op), 3, _hip.ptr(vm), cam.fx,
-                                                  cam.fy, cam.cx, cam.cy, cam.W, cam.H, EPS2D, _hip.ptr(rows), _hip.ptr(v_means3d),
-                                                  _hip.ptr(v_scales), _hip.ptr(v_quats), _hip.ptr(v_opac), _hip.ptr(v_colors),
-                                                  _hip.stream(dev)), "ms_render_bwd_finish")
+                if ctx.densify is None:
+                    _hip.check(L.ms_render_bwd_finish(N, _hip.ptr(m3), _hip.ptr(sc), 1, _hip.ptr(qu), _hip.ptr(op), 3, _hip.ptr(vm), cam.fx,
+                                                      cam.fy, cam.cx, cam.cy, cam.W, cam.H, EPS2D, _hip.ptr(rows), _hip.ptr(v_means3d),
+                                                      _hip.ptr(v_scales), _hip.ptr(v_quats), _hip.ptr(v_opac), _hip.ptr(v_colors),
+                                                      _hip.stream(dev)), "ms_render_bwd_finish")
+                else:   # the same finish, also updating the densification statistics -- once per frame (retain_graph)
+                    dst, ctx.densify = ctx.densify, None
+                    _hip.check(L.ms_render_bwd_finish_densify(
+                        N, _hip.ptr(m3), _hip.ptr(sc), 1, _hip.ptr(qu), _hip.ptr(op), 3, _hip.ptr(vm), cam.fx, cam.fy, cam.cx, cam.cy,
+                        cam.W, cam.H, EPS2D, _hip.ptr(rows), _hip.ptr(v_means3d), _hip.ptr(v_scales), _hip.ptr(v_quats), _hip.ptr(v_opac),
+                        _hip.ptr(v_colors), cam.near, cam.far, _hip.ptr(dst.grad2d), _hip.ptr(dst.count), _hip.ptr(dst.max_radii),
+                        _hip.stream(dev)), "ms_render_bwd_finish_densify")
                 if bev:
                     bev[2].record()
                 if fronts:
@@ -213,6 +231,7 @@ class _RenderFusedHip(torch.autograd.Function):
             # one library call: the backward rasteriser (staging from the frame's ready-made records) and the backward
             # projection, on the scratch the forward call left behind
             else:
+              assert ctx.densify is None, "densification statistics are updated on lean frames only"
               _hip.check(L.ms_render_bwd(
                 N, _hip.ptr(m3), _hip.ptr(sc), 1, _hip.ptr(qu), _hip.ptr(op), _hip.ptr(col), C, _hip.ptr(vm), cam.fx, cam.fy,
                 cam.cx, cam.cy, cam.W, cam.H, EPS2D, ts, _hip.ptr(bg), _hip.ptr(ws), ws.numel(), _hip.ptr(isect),
@@ -226,11 +245,12 @@ class _RenderFusedHip(torch.autograd.Function):
         v_bg = None
         if bg is not None and ctx.needs_input_grad[5]:
             v_bg = ((1.0 - alphas)[..., None] * v_img).sum(dim=(0, 1))
-        return v_means3d, v_scales, v_quats, v_opac, v_colors, v_bg, None, None
+        return v_means3d, v_scales, v_quats, v_opac, v_colors, v_bg, None, None, None
 
 
-def project_gaussians_autograd(means3d, scales, quats, opacities, camera: Camera):
-    return _ProjectHip.apply(means3d, scales, quats, opacities, camera)
+def project_gaussians_autograd(means3d, scales, quats, opacities, camera: Camera, densify=None):
+    """densify: a DensifyStats (densify.py) that the backward updates with its v_means2d and this forward's radii."""
+    return _ProjectHip.apply(means3d, scales, quats, opacities, camera, densify)
 
 
 def rasterize_gaussians_autograd(means2d, conics, colors, opacities, background, tile_ranges,
@@ -241,7 +261,7 @@ def rasterize_gaussians_autograd(means2d, conics, colors, opacities, background,
 
 def render_gaussians_trainable(means3d, scales, quats, opacities, features, camera: Camera,
                                background_color=None, tile_size: int = 16, sh_degree=None,
-                               stagewise: bool = False):
+                               stagewise: bool = False, densify: Optional[DensifyStats] = None):
     """Differentiable twin of ``render_gaussians(backend="hip")``: grads for means3d, scales
     (log-space), quats, opacities and colours (BASELINE config 3).  With ``sh_degree`` and
     features of shape (N, K, 3) the colours are view-dependent SH (sh.py): gradients then reach
@@ -250,9 +270,16 @@ def render_gaussians_trainable(means3d, scales, quats, opacities, features, came
     The forward is the inference path's single library call (fused projection + counting, tight
     binning, sync-free emit + rasterise) with the backward's per-pixel records switched on;
     ``stagewise=True`` runs the three per-stage autograd functions instead (gsplat-exact lists,
-    one host sync) -- same image, same gradients."""
+    one host sync) -- same image, same gradients.
+
+    ``densify``: a ``DensifyStats`` of N entries on the Gaussians' device (ValueError otherwise) that
+    the backward updates, once, on its stream with this view's densification statistics (densify.py).
+    The lean fused frame (three float32 channels, a tile size that is a multiple of 16) updates them
+    inside its backward projection; any other frame takes the per-stage path for it."""
     _hip.require_cuda(means3d, scales, quats, opacities, features, what="gaussian tensor")
     dev = means3d.device
+    if densify is not None:
+        densify.check(means3d.shape[0], dev)
     if features.dim() == 3:
         if sh_degree is None:
             raise ValueError("features of shape (N, K, 3) are SH coefficients: pass sh_degree")
@@ -261,15 +288,6 @@ def render_gaussians_trainable(means3d, scales, quats, opacities, features, came
     C = features.shape[-1]
     bg = torch.zeros(C, device=dev) if background_color is None else \
         torch.as_tensor(background_color, dtype=torch.float32, device=dev)
-    if stagewise or features.dtype != torch.float32:
-        means2d, conics, depths, radii = project_gaussians_autograd(means3d, scales, quats, opacities, camera)
-        th, tw = -(-camera.H // tile_size), -(-camera.W // tile_size)
-        with torch.no_grad():
-            ids, ranges = bin_gaussians_to_tiles_hip(means2d, radii, depths, tile_size, tw, th)
-        if ids.numel() == 0:
-            # same zeros image as the inference path (reference render.py:73-76), grad-connected
-            return (means3d.sum() + features.sum()) * 0 + torch.zeros(camera.H, camera.W, C, device=dev)
-        return rasterize_gaussians_autograd(means2d, conics, features, opacities, bg, ranges, ids, camera, tile_size)
     # The differentiable frame's binning grid is free, like the inference frame's (the image and the gradients are
     # sums over the same (pixel, Gaussian) pairs whatever the bins): MOJOSPLAT_TRAIN_BIN_PX = 16 | 32 | 64 picks it for
     # 16-px tiles (measurements; default: the tile size as given).
@@ -278,4 +296,15 @@ def render_gaussians_trainable(means3d, scales, quats, opacities, features, came
         v = os.environ.get("MOJOSPLAT_TRAIN_BIN_PX")
         if v and int(v) in (16, 32, 64):
             bin_px = int(v)
-    return _RenderFusedHip.apply(means3d, scales, quats, opacities.reshape(-1), features, bg, camera, bin_px)
+    # (the statistics ride on the lean frame's backward -- _RenderFusedHip's `lean`; any other frame: the per-stage path)
+    lean = C == 3 and features.dtype == torch.float32 and bin_px % 16 == 0 and os.environ.get("MOJOSPLAT_BWD_QUADS", "1") != "0"
+    if stagewise or features.dtype != torch.float32 or (densify is not None and not lean):
+        means2d, conics, depths, radii = project_gaussians_autograd(means3d, scales, quats, opacities, camera, densify)
+        th, tw = -(-camera.H // tile_size), -(-camera.W // tile_size)
+        with torch.no_grad():
+            ids, ranges = bin_gaussians_to_tiles_hip(means2d, radii, depths, tile_size, tw, th)
+        if ids.numel() == 0:
+            # same zeros image as the inference path (reference render.py:73-76), grad-connected
+            return (means3d.sum() + features.sum()) * 0 + torch.zeros(camera.H, camera.W, C, device=dev)
+        return rasterize_gaussians_autograd(means2d, conics, features, opacities, bg, ranges, ids, camera, tile_size)
+    return _RenderFusedHip.apply(means3d, scales, quats, opacities.reshape(-1), features, bg, camera, bin_px, densify)

@@ -6,9 +6,48 @@
 //   forward took log-scales), v_quats (w.r.t. the un-normalised quaternion).
 // Culled Gaussians (radii == 0) get zero gradients.  Recomputes the forward intermediates in
 // registers instead of storing them: 44 B in + 24 B of upstream grads + 40 B out per Gaussian.
+//
+// Also here: the densification statistics of 3DGS adaptive density control (Kerbl et al. 2023; gsplat's default
+// strategy), accumulated per view into caller-owned f32[N] buffers -- ms_render_bwd_finish_densify (inside the
+// quad-wave backward projection, where v_means2d lives in registers only) and ms_densify_stats_update (from a
+// v_means2d / radii pair the caller already holds).  Semantics: mojosplat_amd/densify.py, update_torch.
 #include "ms_common.hpp"
+#include "project_device.hpp"
 
 namespace {
+
+// The densification statistics of one view: the buffers and the frame's projection (near / far, opacity-aware extent,
+// radius_clip 0), whose verdict decides which Gaussians count.
+struct DensifyArgs {
+    ms::ProjParams P;
+    float half_w, half_h, max_wh;
+    float *grad2d, *count, *max_radii;
+};
+
+// One Gaussian's update; each Gaussian has one owner lane, so plain read-modify-writes.  r0 / r1: its radii in the view
+// (a Gaussian with a zero radius was culled and is left untouched); g0 / g1: dL/dmeans2d in pixels.  Uncontracted and
+// IEEE (sqrt, divide) like the torch definition: count and max_radii are exact, grad2d within an ulp of its square root.
+__device__ __forceinline__ void densify_update(int64_t i, int r0, int r1, float g0, float g1, float half_w, float half_h,
+                                               float max_wh, float *__restrict__ grad2d, float *__restrict__ count,
+                                               float *__restrict__ max_radii) {
+#pragma clang fp contract(off)
+    if (r0 > 0 && r1 > 0) {
+        const float gx = g0 * half_w, gy = g1 * half_h;
+        grad2d[i] += sqrtf(gx * gx + gy * gy);
+        count[i] += 1.0f;
+        max_radii[i] = fmaxf(max_radii[i], (float)max(r0, r1) / max_wh);
+    }
+}
+
+// Hides a pointer's provenance from the optimiser: STATS's projection then loads and computes on values of its own,
+// and nothing of it is merged with the backward's own chain (whose contraction -- and so whose bits -- must not move).
+// (Kept in the global address space, so that its loads stay global_load.)
+template <class T>
+__device__ __forceinline__ const T *opaque(const T *p) {
+    auto g = (const __attribute__((address_space(1))) T *)p;
+    asm volatile("" : "+s"(g));
+    return (const T *)g;
+}
 
 struct ProjBwdParams {
     float fx, fy, cx, cy, eps2d;
@@ -24,7 +63,10 @@ struct ProjBwdParams {
 // (vs = dL/dsigma of a pixel-Gaussian pair, dx = mean - pixel): with the conic (a, b, c) this kernel recomputes anyway,
 // v_mean = (a gx + b gy, b gx + c gy), v_conic = (s1 / 2, s2, s3 / 2), v_opacity = -m0 / opacity.  A Gaussian whose row is
 // all zero was never blended (or culled): zero gradients, no radii needed.
-template <int ROWS>
+// STATS (ROWS == 2 only): every lane also re-projects its Gaussian with the forward's own project_one -- the alive verdict
+// and the radii, which a lean frame never wrote -- and updates the densification statistics D with its vm0 / vm1 (zero
+// for a Gaussian alive but never blended).  The gradients are those of STATS == false, bit for bit.
+template <int ROWS, bool STATS = false>
 __global__ __launch_bounds__(256) void k_project_ewa_bwd(
     int64_t N, const float *__restrict__ means3d, const float *__restrict__ scales,
     const float *__restrict__ quats, const float *__restrict__ viewmat, ProjBwdParams P,
@@ -32,9 +74,16 @@ __global__ __launch_bounds__(256) void k_project_ewa_bwd(
     const float *__restrict__ v_conics, const float *__restrict__ v_depths,
     float *__restrict__ v_means3d, float *__restrict__ v_scales, float *__restrict__ v_quats,
     const float *__restrict__ rows, int cdim, float *__restrict__ v_colors, float *__restrict__ v_opacities,
-    const float *__restrict__ opacities) {
+    const float *__restrict__ opacities, DensifyArgs D) {
+    static_assert(!STATS || ROWS == 2, "the statistics ride on the quad-wave rows");
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
+    int st_r0 = 0, st_r1 = 0;
+    if constexpr (STATS) {
+        const ms::ProjOut o = ms::project_one(i, opaque(means3d), opaque(scales), opaque(quats), opaque(opacities),
+                                              opaque(viewmat), D.P);
+        st_r0 = o.r0; st_r1 = o.r1;
+    }
     float4 row0 = make_float4(0.f, 0.f, 0.f, 0.f), row1 = row0;
     bool visible;
     if constexpr (ROWS == 1) {
@@ -58,6 +107,7 @@ __global__ __launch_bounds__(256) void k_project_ewa_bwd(
         visible = rad.x > 0 && rad.y > 0;
     }
     float o_p[3] = {0.f, 0.f, 0.f}, o_s[3] = {0.f, 0.f, 0.f}, o_q[4] = {0.f, 0.f, 0.f, 0.f};
+    float st_g0 = 0.f, st_g1 = 0.f;
     if (visible) {
         float V[12];
 #pragma unroll
@@ -124,6 +174,7 @@ __global__ __launch_bounds__(256) void k_project_ewa_bwd(
             vka = ROWS ? row0.z : v_conics[3 * i]; vkb = (ROWS ? row0.w : v_conics[3 * i + 1]) * 0.5f;
             vkc = ROWS ? row1.x : v_conics[3 * i + 2];
         }
+        if constexpr (STATS) { st_g0 = vm0; st_g1 = vm1; }
         const float vd = v_depths ? v_depths[i] : 0.f;
         // conic = inverse(cov2d): v_cov2d = -K vK K  (K symmetric; off-diagonal grad halved)
         const float t00 = ka * vka + kb * vkb, t01 = ka * vkb + kb * vkc;
@@ -208,6 +259,22 @@ __global__ __launch_bounds__(256) void k_project_ewa_bwd(
         v_scales[3 * i + k] = o_s[k];
     }
     reinterpret_cast<float4 *>(v_quats)[i] = make_float4(o_q[0], o_q[1], o_q[2], o_q[3]);
+    if constexpr (STATS)
+        densify_update(i, st_r0, st_r1, st_g0, st_g1, D.half_w, D.half_h, D.max_wh, D.grad2d, D.count, D.max_radii);
+}
+
+// ms_densify_stats_update: one lane per Gaussian
+__global__ __launch_bounds__(256) void k_densify_stats_update(int64_t N, const int32_t *__restrict__ radii,
+                                                              const float *__restrict__ v_means2d, float half_w, float half_h,
+                                                              float max_wh, float *__restrict__ grad2d,
+                                                              float *__restrict__ count, float *__restrict__ max_radii) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const int2 r = reinterpret_cast<const int2 *>(radii)[i];
+    if (r.x > 0 && r.y > 0) {
+        const float2 g = reinterpret_cast<const float2 *>(v_means2d)[i];
+        densify_update(i, r.x, r.y, g.x, g.y, half_w, half_h, max_wh, grad2d, count, max_radii);
+    }
 }
 
 }  // namespace
@@ -238,7 +305,7 @@ extern "C" int ms_project_gaussians_bwd(int64_t N, const float *means3d, const f
     MS_REQUIRE(grid <= 0x7fffffff, MS_ERR_INVALID_ARG, "project_bwd: N too large");
     hipLaunchKernelGGL(k_project_ewa_bwd<0>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, N, means3d,
                        scales, quats, viewmat, P, radii, v_means2d, v_conics, v_depths, v_means3d, v_scales,
-                       v_quats, nullptr, 0, nullptr, nullptr, nullptr);
+                       v_quats, nullptr, 0, nullptr, nullptr, nullptr, DensifyArgs{});
     MS_LAUNCH_CHECK();
     return MS_OK;
 }
@@ -270,11 +337,67 @@ int ms::project_bwd_from_rows(int64_t N, const float *means3d, const float *scal
     if (raw)
         hipLaunchKernelGGL(k_project_ewa_bwd<2>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, N, means3d,
                            scales, quats, viewmat, P, radii, nullptr, nullptr, nullptr, v_means3d, v_scales, v_quats, rows, CDIM,
-                           v_colors, v_opacities, raw_rows_opacities);
+                           v_colors, v_opacities, raw_rows_opacities, DensifyArgs{});
     else
         hipLaunchKernelGGL(k_project_ewa_bwd<1>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, N, means3d,
                            scales, quats, viewmat, P, radii, nullptr, nullptr, nullptr, v_means3d, v_scales, v_quats, rows, CDIM,
-                           v_colors, v_opacities, nullptr);
+                           v_colors, v_opacities, nullptr, DensifyArgs{});
+    MS_LAUNCH_CHECK();
+    return MS_OK;
+}
+
+// ms_render_bwd_finish with the densification statistics: k_project_ewa_bwd<2, true>
+extern "C" int ms_render_bwd_finish_densify(int64_t N, const float *means3d, const float *scales, int scales_are_log,
+                                            const float *quats, const float *opacities, int CDIM, const float *viewmat,
+                                            float fx, float fy, float cx, float cy, int W, int H, float eps2d,
+                                            const float *rows, float *v_means3d, float *v_scales, float *v_quats,
+                                            float *v_opacities, float *v_colors, float near_plane, float far_plane,
+                                            float *grad2d, float *count, float *max_radii, void *stream) {
+    MS_REQUIRE(N >= 0 && CDIM == 3 && v_means3d && v_scales && v_quats && v_opacities && v_colors && grad2d && count && max_radii,
+               MS_ERR_INVALID_ARG, "render_bwd_finish_densify: bad argument");
+    if (N == 0) return MS_OK;
+    MS_REQUIRE(means3d && scales && quats && viewmat && rows && opacities, MS_ERR_INVALID_ARG,
+               "render_bwd_finish_densify: null pointer");
+    MS_REQUIRE(W > 0 && H > 0 && fx != 0.f && fy != 0.f, MS_ERR_INVALID_ARG, "render_bwd_finish_densify: bad camera");
+    MS_REQUIRE(((uintptr_t)quats & 15) == 0 && ((uintptr_t)v_quats & 15) == 0 && ((uintptr_t)rows & 15) == 0,
+               MS_ERR_INVALID_ARG, "render_bwd_finish_densify: quats / v_quats / rows must be 16-byte aligned");
+    MS_REQUIRE((((uintptr_t)grad2d | (uintptr_t)count | (uintptr_t)max_radii) & 3) == 0, MS_ERR_INVALID_ARG,
+               "render_bwd_finish_densify: statistics must be 4-byte aligned");
+    ProjBwdParams P;
+    P.fx = fx; P.fy = fy; P.cx = cx; P.cy = cy; P.eps2d = eps2d;
+    const float tan_fovx = 0.5f * (float)W / fx, tan_fovy = 0.5f * (float)H / fy;
+    P.lim_x_pos = ((float)W - cx) / fx + 0.3f * tan_fovx;
+    P.lim_x_neg = cx / fx + 0.3f * tan_fovx;
+    P.lim_y_pos = ((float)H - cy) / fy + 0.3f * tan_fovy;
+    P.lim_y_neg = cy / fy + 0.3f * tan_fovy;
+    P.scales_are_log = scales_are_log;
+    DensifyArgs D;
+    // the frame's projection: its planes, the opacity-aware extent and no radius clip (pipeline.hip, ms_render_fwd)
+    D.P = ms::make_proj_params(fx, fy, cx, cy, W, H, eps2d, near_plane, far_plane, 0.0f, scales_are_log, true);
+    D.half_w = 0.5f * (float)W; D.half_h = 0.5f * (float)H; D.max_wh = (float)(W > H ? W : H);
+    D.grad2d = grad2d; D.count = count; D.max_radii = max_radii;
+    const int64_t grid = ms::ceil_div(N, 256);
+    MS_REQUIRE(grid <= 0x7fffffff, MS_ERR_INVALID_ARG, "render_bwd_finish_densify: N too large");
+    hipLaunchKernelGGL((k_project_ewa_bwd<2, true>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, N, means3d, scales,
+                       quats, viewmat, P, nullptr, nullptr, nullptr, nullptr, v_means3d, v_scales, v_quats, rows, CDIM, v_colors,
+                       v_opacities, opacities, D);
+    MS_LAUNCH_CHECK();
+    return MS_OK;
+}
+
+extern "C" int ms_densify_stats_update(int64_t N, int W, int H, const int32_t *radii, const float *v_means2d, float *grad2d,
+                                       float *count, float *max_radii, void *stream) {
+    MS_REQUIRE(N >= 0, MS_ERR_INVALID_ARG, "densify_stats_update: N < 0");
+    if (N == 0) return MS_OK;
+    MS_REQUIRE(radii && v_means2d && grad2d && count && max_radii, MS_ERR_INVALID_ARG, "densify_stats_update: null pointer");
+    MS_REQUIRE(W > 0 && H > 0, MS_ERR_INVALID_ARG, "densify_stats_update: bad image size");
+    MS_REQUIRE((((uintptr_t)radii | (uintptr_t)v_means2d) & 7) == 0 &&
+                   (((uintptr_t)grad2d | (uintptr_t)count | (uintptr_t)max_radii) & 3) == 0,
+               MS_ERR_INVALID_ARG, "densify_stats_update: radii / v_means2d must be 8-byte, statistics 4-byte aligned");
+    const int64_t grid = ms::ceil_div(N, 256);
+    MS_REQUIRE(grid <= 0x7fffffff, MS_ERR_INVALID_ARG, "densify_stats_update: N too large");
+    hipLaunchKernelGGL(k_densify_stats_update, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, N, radii, v_means2d,
+                       0.5f * (float)W, 0.5f * (float)H, (float)(W > H ? W : H), grad2d, count, max_radii);
     MS_LAUNCH_CHECK();
     return MS_OK;
 }
