@@ -125,8 +125,7 @@ class _RenderFusedHip(torch.autograd.Function):
         # the quad-wave rasteriser.  Anything else keeps last_ids and fully sorted lists for the older kernel.
         # (round 5, advisor: the quad-wave kernel works in 16x16 blocks -- ms_render_bwd only takes it when the tile size is a
         # multiple of 16; a frame at tile_size 8 / 24 / ... keeps last_ids and fully sorted lists for the older kernel)
-        lean = colors.shape[1] == 3 and colors.dtype == torch.float32 and tile_size % 16 == 0 and \
-            os.environ.get("MOJOSPLAT_BWD_QUADS", "1") != "0"
+        lean = colors.shape[1] == 3 and colors.dtype == torch.float32 and tile_size % 16 == 0
         key = None
         if lean and tile_size == _render.TILE_SIZE and "MOJOSPLAT_TRAIN_BIN_PX" not in os.environ:
             explicit = _render._env_bin_px()
@@ -297,7 +296,7 @@ def render_gaussians_trainable(means3d, scales, quats, opacities, features, came
         if v and int(v) in (16, 32, 64):
             bin_px = int(v)
     # (the statistics ride on the lean frame's backward -- _RenderFusedHip's `lean`; any other frame: the per-stage path)
-    lean = C == 3 and features.dtype == torch.float32 and bin_px % 16 == 0 and os.environ.get("MOJOSPLAT_BWD_QUADS", "1") != "0"
+    lean = C == 3 and features.dtype == torch.float32 and bin_px % 16 == 0
     if stagewise or features.dtype != torch.float32 or (densify is not None and not lean):
         means2d, conics, depths, radii = project_gaussians_autograd(means3d, scales, quats, opacities, camera, densify)
         th, tw = -(-camera.H // tile_size), -(-camera.W // tile_size)

@@ -821,9 +821,7 @@ extern "C" int ms_render_bwd(int64_t N, const float *means3d, const float *scale
     const bool packed_rows = CDIM <= 4 && rb > 0 && M > 0 && N <= 0x7fffffffll;
     // a 3-channel frame whose image the caller still holds: the quad-wave kernel (rasterize_bwdq.hip) walks the frame's own
     // lists front to back from the records and leaves raw sums, which the backward projection finishes
-    // (MOJOSPLAT_BWD_QUADS=0: the older kernel, which needs last_ids)
-    static const int quads_on = [] { const char *e = getenv("MOJOSPLAT_BWD_QUADS"); return e ? atoi(e) != 0 : 1; }();
-    if (render_colors && records && packed_rows && tile_size % 16 == 0 && (quads_on || !last_ids)) {
+    if (render_colors && records && packed_rows && tile_size % 16 == 0) {
         if (int rc = render_bwd_rows_impl(N, CDIM, W, H, tile_size, 0, th, backgrounds, workspace, workspace_bytes, isect_buf, isect_bytes,
                                           host_info, render_colors, render_alphas, v_render_colors, v_render_alphas, (float *)bw, stream_))
             return rc;

@@ -81,7 +81,6 @@ struct RasterArgs {
     float4 *zero_mem;      // round 6: memory the launch zeroes on its way (16-byte units: zero_total of them, zero_per_wave a wave), or null
     unsigned zero_per_wave;
     size_t zero_total;
-    int nvb;               // persistent launch (round 6): virtual workgroup indices in all (what a one-block-per-wave launch's grid would be)
 };
 
 constexpr float kLog2e = 1.4426950408889634f;
@@ -161,18 +160,6 @@ __device__ __forceinline__ void wave_lds_sync() {
 #ifndef MS_RASTER_GROUP
 #define MS_RASTER_GROUP 2
 #endif
-#ifndef MS_RASTER_LOCAL_CONST
-#define MS_RASTER_LOCAL_CONST 1
-#endif
-#ifndef MS_RASTER_HALF_STREAMS
-#define MS_RASTER_HALF_STREAMS 0   // 1: the measurement variant of profiles/r06_raster_halfquad.md (a stream per 8x4 half-quad)
-#endif
-#ifndef MS_RASTER_CHAINS
-#define MS_RASTER_CHAINS 0     // 1: the measurement variant of profiles/r06_raster_startup.md (waves that walk chains of blocks)
-#endif
-#ifndef MS_RASTER_EXPANDED
-#define MS_RASTER_EXPANDED 0   // 1: the measurement variant of profiles/r05_raster_expanded.md (never the shipped library)
-#endif
 #ifndef MS_RASTER_UNROLL
 #define MS_RASTER_UNROLL 2
 #endif
@@ -206,18 +193,6 @@ struct RasterStage {
     float4 b[kSlots];        // c', log2(opacity), (r, g | index in batch, -)
 };
 
-// Round 6: PERSISTENT waves (profiles/r06_raster_startup.md).  A wave that is its own workgroup pays its start-up chain --
-// tile range -> ids -> records -> LDS, three dependent round trips -- alone, before its first blend: 48 % of all wave cycles at
-// config 2, 28 % on an edge band of config 5, 14 % at config 3 (scripts/raster_waves.py).  A persistent wave walks several
-// blocks (virtual workgroup indices vb, vb + grid, ...) and issues the NEXT block's first ids and records where the current
-// block's list has none left to prefetch -- into the very registers the within-list prefetch uses, so no register is added:
-//   carry = 1: r_g holds the next block's first batch of ids;  2: r_a / r_b / r_c its records and r_g its second batch of ids.
-struct RasterNext {
-    int carry;            // in: what the previous block of this wave left for THIS block; out: what this block leaves
-    int valid;            // a next block exists and its list is not empty
-    int start, end;       // the next block's list (as raster_tile will compute it)
-};
-
 // a tile's list as the rasteriser walks it: [start, end) of the sorted ids, end_all = where the whole list ends
 __device__ __forceinline__ void raster_list_bounds(const RasterArgs &A, const int tile, int &start, int &end, int &end_all) {
     // clamped to the list length the caller vouches for (a sync-free frame passes its buffer capacity)
@@ -237,16 +212,10 @@ __device__ __forceinline__ bool raster_block_in_band(const RasterArgs &A, const 
 
 // One wave's share of a 16x16 block: NQ quads of block `sub` of tile `tile`, starting at quad part * NQ.  s_q: the
 // wave's NQ staging blocks.
-// HALF (round 6, NQ == 1 only): the wave's two 32-lane halves -- rows 0-3 and rows 4-7 of its 8x8 quad -- walk compacted
-// streams of their OWN: an entry that reaches only one half costs the other half nothing, and the loop runs for the longer
-// of the two streams (profiles/r06_raster_halfquad.md).
-template <int CP, typename ColorT, bool AUX, int NQ, bool PACKED, bool LISTS = false, bool PERSIST = false, bool HALF = false>
+template <int CP, typename ColorT, bool AUX, int NQ, bool PACKED, bool LISTS = false>
 __device__ __forceinline__ void raster_tile(const RasterArgs &A, const int tile, const int sub, const int part,
                                             RasterStage<CP, AUX> *s_q, const int diag_slot,
-                                            float4 &r_a, float4 &r_b, float4 &r_c, int &r_g, RasterNext &nx) {
-    static_assert(!PERSIST || (PACKED && !AUX && !LISTS), "persistent waves: the plain kernel on ready-made records");
-    static_assert(!HALF || (NQ == 1 && PACKED && !AUX && !LISTS && !PERSIST && CP == 3), "half-quad streams: the plain one-quad kernel");
-    constexpr int NS = HALF ? 2 : NQ;   // compacted streams a wave keeps (and votes on)
+                                            float4 &r_a, float4 &r_b, float4 &r_c, int &r_g) {
     static_assert(!LISTS || (PACKED && !AUX), "quad lists: the plain 3-channel kernel on ready-made records");
     static_assert(!PACKED || CP == 3, "ready-made records carry three channels");
     using Stage = RasterStage<CP, AUX>;
@@ -255,8 +224,6 @@ __device__ __forceinline__ void raster_tile(const RasterArgs &A, const int tile,
     const int qbase = NQ == 4 ? 0 : part * NQ;
     const int tile_y = tile / A.tw, tile_x = tile - tile_y * A.tw;
     const int sub_y = sub / A.nsx, sub_x = sub - sub_y * A.nsx;
-    const int have = PERSIST ? nx.carry : 0;   // (wave-uniform) what the wave's previous block fetched of this one's list
-    if constexpr (PERSIST) nx.carry = 0;
     if (!raster_block_in_band(A, tile, sub)) {   // a band cut at 16-px rows inside coarser tiles: blocks outside it are not this call's
         if constexpr (LISTS) {   // (nothing of this block is rendered: its quads leave empty lists)
             if ((threadIdx.x & 63) < NQ) A.quad_counts[(size_t)tile * A.quad_nq + sub * 4 + qbase + (threadIdx.x & 63)] = 0;
@@ -268,9 +235,6 @@ __device__ __forceinline__ void raster_tile(const RasterArgs &A, const int tile,
     const int bx = tile_x * A.ts + sub_x * 16, by = tile_y * A.ts + sub_y * 16;
     const int ox = sub_x * 16 + lx, oy = sub_y * 16 + ly;
     const float px0 = (float)(bx + lx) + 0.5f, py0 = (float)(by + ly) + 0.5f;
-#if MS_RASTER_EXPANDED
-    const float ux = (float)lx - 3.5f, uy = (float)ly - 3.5f;   // the pixel centre's offset from its quad's centre
-#endif
 
     constexpr float kInf = __builtin_huge_valf();
     // kq: the lane's multiplier of the flush select (ms::kFlushK while the pixel is live, 0 once it has stopped
@@ -297,8 +261,8 @@ __device__ __forceinline__ void raster_tile(const RasterArgs &A, const int tile,
     // headline variant a spilled VGPR -- 8 MB of scratch writes per frame, WRITE_SIZE 25.7 -> 33.6 MB)
     flush_fp32_denormals();
 
-    // what the staging lane holds of its entry: the record's three words (PACKED: r_a / r_b / r_c, the caller's -- a persistent
-    // wave carries them from block to block), or the per-stage fields
+    // what the staging lane holds of its entry: the record's three words (PACKED: r_a / r_b / r_c, the caller's), or the
+    // per-stage fields
     float r_ca = 0.f, r_cb = 0.f, r_cc = 0.f, r_op = 0.f;
     float r_col[CP];
     // LISTS: the Gaussian whose record r_a / r_b / r_c hold; how many entries each quad has left so far; whether it still has
@@ -343,40 +307,13 @@ __device__ __forceinline__ void raster_tile(const RasterArgs &A, const int tile,
             }
         }
     };
-
-    // PERSIST: the next block's first ids go where this list has nothing left to fetch ahead (r_g is free then); its records
-    // follow on this list's last batch, once that batch is staged (r_a / r_b / r_c are free then)
-    bool rg_next = false;   // r_g holds (or is loading) the next block's first batch of ids
-    int rg_age = 0;         // blend loops since they were asked for: >= 1 -> they have landed behind one
     auto fetch_ahead = [&](int b) __attribute__((always_inline)) {
         if (b < end) fetch_id(b);
-        else if constexpr (PERSIST) {
-            if (nx.valid && !rg_next) {
-                const int idx = nx.start + lane;
-                r_g = idx < nx.end ? A.flatten_ids[idx] : 0;
-                rg_next = true;
-                rg_age = 0;
-            }
-        }
-    };
-    auto gather_next = [&]() __attribute__((always_inline)) {
-        if constexpr (PERSIST) {
-            const int idx = nx.start + lane;
-            if (idx < nx.end) {
-                const int g = min(max(r_g, 0), A.n_gauss - 1);
-                const float4 *rec = A.records + 3 * (size_t)g;
-                r_a = rec[0]; r_b = rec[1]; r_c = rec[2];
-            }
-            const int idx2 = idx + kBatch;
-            r_g = idx2 < nx.end ? A.flatten_ids[idx2] : 0;
-            rg_next = false;
-            nx.carry = 2;
-        }
     };
     if (start < end) {
-        if (have == 0) fetch_id(start);
-        if (have <= 1) gather(start);
-        if (have <= 1 || start + kBatch >= end) fetch_ahead(start + kBatch);
+        fetch_id(start);
+        gather(start);
+        fetch_ahead(start + kBatch);
     }
     for (int b0 = start; b0 < end; b0 += kBatch) {
         // --- stage this batch: reach of the alpha >= 1/255 ellipse -> quad votes -> compacted records in LDS
@@ -399,10 +336,10 @@ __device__ __forceinline__ void raster_tile(const RasterArgs &A, const int tile,
                 npd = true;
             } else if (smax > -kInf) {
 #pragma unroll
-                for (int qi = 0; qi < NS; ++qi) {
-                    const int q = HALF ? qbase : qbase + qi;
+                for (int qi = 0; qi < NQ; ++qi) {
+                    const int q = qbase + qi;
                     const float xl = fbx + (float)((q & 1) * 8) - r_a.x, xh = xl + 7.0f;   // rectangle - mean
-                    const float yl = fby + (float)((q >> 1) * 8 + (HALF ? 4 * qi : 0)) - r_a.y, yh = yl + (HALF ? 3.0f : 7.0f);
+                    const float yl = fby + (float)((q >> 1) * 8) - r_a.y, yh = yl + 7.0f;
                     const bool in_x = xl <= 0.f && xh >= 0.f, in_y = yl <= 0.f && yh >= 0.f;
                     float best = (in_x && in_y) ? 0.f : 3.0e38f;
                     if (!in_x) {
@@ -419,17 +356,9 @@ __device__ __forceinline__ void raster_tile(const RasterArgs &A, const int tile,
                 }
             }
         }
-        unsigned long long B[NS];
+        unsigned long long B[NQ];
 #pragma unroll
-        for (int qi = 0; qi < NS; ++qi) B[qi] = __ballot((mask >> qi) & 1);
-        int n_loop = 0;   // HALF: the longer of the two streams
-        if constexpr (HALF) n_loop = max(__popcll(B[0]), __popcll(B[1]));
-#if MS_RASTER_EXPANDED
-        // (measurement variant, round 5: log2(alpha) as the quadratic EXPANDED about the quad's centre -- five FMAs on two
-        // lane constants instead of two subtractions + five: the staging lane leaves a', b', c', D, E, F per reached quad.
-        // Batches that need the sigma >= 0 test keep the plain records.)
-        const bool expanded = PACKED && __ballot(npd) == 0;
-#endif
+        for (int qi = 0; qi < NQ; ++qi) B[qi] = __ballot((mask >> qi) & 1);
 
         wave_lds_sync();  // LDS reads of the previous batch are complete
         // every reached quad gets the record at its rank among the quad's entries (list order is kept); the
@@ -440,7 +369,7 @@ __device__ __forceinline__ void raster_tile(const RasterArgs &A, const int tile,
         if constexpr (CP == 3) r_c.y = __int_as_float(lane);
         else r_b.z = __int_as_float(lane);
 #pragma unroll
-        for (int qi = 0; qi < NS; ++qi) {
+        for (int qi = 0; qi < NQ; ++qi) {
             Stage &S = s_q[qi];
             const unsigned long long b = B[qi];
             const int n = __popcll(b);
@@ -449,22 +378,8 @@ __device__ __forceinline__ void raster_tile(const RasterArgs &A, const int tile,
                 if constexpr (LISTS) {
                     if (q_live[qi]) A.quad_lists[q_at[qi] + (unsigned long long)(unsigned)pos] = g_staged;
                 }
-#if MS_RASTER_EXPANDED
-                if (expanded) {
-                    const int q = qbase + qi;
-                    const float U = r_a.x - ((float)(bx + (q & 1) * 8) + 4.0f), V = r_a.y - ((float)(by + (q >> 1) * 8) + 4.0f);
-                    const float D = -fmaf(2.0f * r_a.z, U, r_a.w * V), E = -fmaf(2.0f * r_b.x, V, r_a.w * U);
-                    const float F = fmaf(U, fmaf(r_a.z, U, r_a.w * V), fmaf(r_b.x * V, V, r_b.y));
-                    S.a[pos] = make_float4(r_a.z, r_a.w, r_b.x, D);
-                    S.b[pos] = make_float4(E, F, r_b.z, r_b.w);
-                } else {
-                    S.a[pos] = r_a;
-                    S.b[pos] = r_b;
-                }
-#else
                 S.a[pos] = r_a;
                 S.b[pos] = r_b;
-#endif
                 if constexpr (CP == 3) {
                     if constexpr (AUX) reinterpret_cast<float2 *>(S.col)[pos] = make_float2(r_c.x, r_c.y);
                     else S.col[pos] = r_c.x;
@@ -477,16 +392,11 @@ __device__ __forceinline__ void raster_tile(const RasterArgs &A, const int tile,
             if constexpr (LISTS) {
                 if (q_live[qi]) q_at[qi] += (unsigned long long)(unsigned)n;
             }
-            // (HALF: the shorter stream is padded with neutral records up to the longer one's end: the halves walk in lockstep)
-            if (HALF ? (n + lane < n_loop + kGroup) : (lane < kGroup)) {
-                // (the two constants are made HERE: hoisted out of the batch loop as eight registers of zeros and -inf they
-                // were the first thing the persistent kernel spilled)
+            if (lane < kGroup) {
+                // (the two constants are made HERE, behind an empty asm: hoisted out of the batch loop, they would hold eight
+                // registers of zeros and -inf across the whole walk)
                 float zero = 0.f, ninf = -kInf;
-#if MS_RASTER_LOCAL_CONST
                 asm volatile("" : "+v"(zero), "+v"(ninf));
-#else
-                if constexpr (PERSIST) asm volatile("" : "+v"(zero), "+v"(ninf));
-#endif
                 S.a[n + lane] = make_float4(zero, zero, zero, zero);
                 S.b[n + lane] = make_float4(zero, ninf, zero, zero);   // log2(alpha) = -inf: alpha = 0, never a hit
                 if constexpr (CP == 3) {
@@ -503,10 +413,6 @@ __device__ __forceinline__ void raster_tile(const RasterArgs &A, const int tile,
         if (b0 + kBatch < end) {  // next batch's data and the one after's ids fly during compositing
             gather(b0 + kBatch);
             fetch_ahead(b0 + 2 * kBatch);
-        } else if constexpr (PERSIST) {
-            // the list's last batch is staged: the next block's records fly during its compositing (ids asked for a blend
-            // loop ago have landed; a one-batch list's are still in flight -- its records go out behind the loop instead)
-            if (rg_next && rg_age >= 1) gather_next();
         }
         MS_DIAG_ONLY(if (diag_batches == 0) diag_first = __builtin_amdgcn_s_memtime() - diag_c0; ++diag_batches;)   // (first batch staged: the start-up chain range -> ids -> records -> LDS is behind the wave)
 
@@ -522,8 +428,8 @@ __device__ __forceinline__ void raster_tile(const RasterArgs &A, const int tile,
                 const int q = qbase + qi;
                 if (!__any(kq[qi] != 0.f)) continue;  // every pixel of this quad is finished (or outside)
                 const float px = px0 + (float)((q & 1) * 8), py = py0 + (float)((q >> 1) * 8);
-                const Stage &S = s_q[HALF ? (lane >> 5) : qi];   // (HALF: a per-lane LDS base, the same offsets)
-                const int n = HALF ? n_loop : __popcll(B[qi]);
+                const Stage &S = s_q[qi];
+                const int n = __popcll(B[qi]);
                 // kGroup records per trip: their LDS reads go out together, the kGroup log2(alpha) chains and
                 // exp2 are independent of each other (and of the T chain), then the blends run in list order
                 // one trip: kGroup records from LDS address k0, transmittance t in and out (by value, so that two
@@ -558,20 +464,9 @@ __device__ __forceinline__ void raster_tile(const RasterArgs &A, const int tile,
                     float m[kGroup], v[kGroup];
 #pragma unroll
                     for (int j = 0; j < kGroup; ++j) {
-#if MS_RASTER_EXPANDED
-                        float la;
-                        if constexpr (!CHECK && PACKED) {
-                            // a' ux^2 + b' ux uy + c' uy^2 + D ux + E uy + F, Horner: (a, b, c, D) | (E, F, ...)
-                            la = fmaf(ux, fmaf(ra[j].x, ux, fmaf(ra[j].y, uy, ra[j].w)), fmaf(uy, fmaf(ra[j].z, uy, rb[j].x), rb[j].y));
-                        } else {
-                            const float dx = ra[j].x - px, dy = ra[j].y - py;
-                            la = fmaf(dx, fmaf(ra[j].z, dx, ra[j].w * dy), fmaf(rb[j].x * dy, dy, rb[j].y));
-                        }
-#else
                         const float dx = ra[j].x - px, dy = ra[j].y - py;
                         // log2(alpha) = log2(o) - sigma*log2(e), with log2(o) riding in the FMA chain
                         const float la = fmaf(dx, fmaf(ra[j].z, dx, ra[j].w * dy), fmaf(rb[j].x * dy, dy, rb[j].y));
-#endif
                         float alpha = __builtin_amdgcn_exp2f(la);
                         if constexpr (CHECK) {
                             alpha = fminf(ms::kMaxAlpha, alpha);
@@ -638,14 +533,7 @@ __device__ __forceinline__ void raster_tile(const RasterArgs &A, const int tile,
         };
         if (check_sigma) blend_batch(std::true_type{});
         else blend_batch(std::false_type{});
-        if constexpr (PERSIST) {
-            ++rg_age;
-            if (rg_next && b0 + kBatch >= end) gather_next();
-        }
         if (!any_live) break;
-    }
-    if constexpr (PERSIST) {
-        if (rg_next) nx.carry = 1;   // (the walk ended early: the ids are all the next block gets)
     }
     if constexpr (LISTS) {
         if (lane == 0) {
@@ -750,64 +638,21 @@ __device__ __forceinline__ bool raster_map_block(const RasterArgs &A, const int 
     return true;
 }
 
-template <int CP, typename ColorT, bool AUX, int NQ, bool PACKED, bool LISTS = false, bool PERSIST = false, bool HALF = false>
+template <int CP, typename ColorT, bool AUX, int NQ, bool PACKED, bool LISTS = false>
 __global__ __launch_bounds__(64, (CP <= 4 ? (NQ == 2 ? MS_RASTER_MINW2 : AUX ? MS_RASTER_MINW_AUX : MS_RASTER_MINW) : 1)) void k_rasterize_fwd(RasterArgs A) {
-    __shared__ RasterStage<CP, AUX> s_stage[HALF ? 2 : NQ];
+    __shared__ RasterStage<CP, AUX> s_stage[NQ];
+    // (the staging lane's id and record, raster_tile's by reference: declared inside it instead, the 32-channel instances
+    // allocate registers differently and one spills a VGPR more)
     float4 r_a = make_float4(0.f, 0.f, 0.f, 0.f), r_b = r_a, r_c = r_a;
     int r_g = 0;
-    RasterNext nx{0, 0, 0, 0};
     if (A.zero_mem) {   // (uniform) this wave's slice of the memory the launch zeroes: stores nobody waits for
         const size_t i0 = (size_t)blockIdx.x * A.zero_per_wave;
         for (unsigned i = threadIdx.x & 63u; i < A.zero_per_wave; i += 64u)
             if (i0 + i < A.zero_total) A.zero_mem[i0 + i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    if constexpr (!PERSIST) {
-        int tile, sub, part, slot;
-        if (!raster_map_block<NQ>(A, (int)blockIdx.x, tile, sub, part, slot)) return;
-        raster_tile<CP, ColorT, AUX, NQ, PACKED, LISTS, false, HALF>(A, tile, sub, part, s_stage, slot, r_a, r_b, r_c, r_g, nx);
-    } else {
-        // A persistent wave: virtual indices blockIdx, blockIdx + grid, ... (the grid is a multiple of 8 x the waves per
-        // block, so an index keeps its XCD label and a block's waves stay neighbours).  Odd rounds run through the grid
-        // backwards WITHIN the XCD's share: the order is heaviest first, so a wave that drew a heavy block of one round
-        // draws a light one of the next.  Launched for frames with a heaviest-first order of whole tiles only (nsub a power
-        // of two: 1, 4, 16): the index -> block mapping is then shifts and one load, nothing to keep in scalar registers
-        // across a block (the general mapping's divisions spilled 66 of them to vector lanes).
-        constexpr int kParts = 4 / NQ;
-        const int G = (int)gridDim.x;
-        const int sh = A.nsx == 1 ? 0 : A.nsx == 2 ? 2 : 4;   // log2(nsub)
-        // -> tile | sub << 24 | part << 28, or -1
-        auto block_of = [&](int round) __attribute__((always_inline)) -> int {
-            const int w = (int)blockIdx.x;
-            const int x = (round & 1) ? ((((G >> 3) - 1 - (w >> 3)) << 3) | (w & 7)) : w;
-            const int vb = round * G + x;
-            if (vb >= A.nvb) return -1;
-            const int j = vb >> 3;
-            const int part = kParts > 1 ? j % kParts : 0;
-            const int wg = kParts > 1 ? (((j / kParts) << 3) | (vb & 7)) : vb;
-            if (wg >= A.ngrid) return -1;
-            const int e = (((wg >> 3) >> sh) << 3) | (wg & 7);
-            if (e >= (A.nblocks >> sh)) return -1;   // (the grid is padded to 8 tiles)
-            return A.order[e] | (((wg >> 3) & ((1 << sh) - 1)) << 24) | (part << 28);
-        };
-        int cur = block_of(0);
-        for (int round = 0; round * G < A.nvb; ++round) {
-            // the block after this one: its list's bounds are needed before this block's last batch
-            const int nxt = block_of(round + 1);
-            nx.valid = 0;
-            if (nxt >= 0 && raster_block_in_band(A, nxt & 0xffffff, (nxt >> 24) & 15)) {
-                int e_all;
-                raster_list_bounds(A, nxt & 0xffffff, nx.start, nx.end, e_all);
-                nx.valid = nx.start < nx.end ? 1 : 0;
-            }
-            if (cur >= 0) {
-                const int tile = cur & 0xffffff, sub = (cur >> 24) & 15, part = cur >> 28;
-                int slot = 0;
-                MS_DIAG_ONLY(slot = (round * G + (int)blockIdx.x);)   // (diagnostic stamps: one slot per (wave, round))
-                raster_tile<CP, ColorT, AUX, NQ, PACKED, LISTS, true>(A, tile, sub, part, s_stage, slot, r_a, r_b, r_c, r_g, nx);
-            } else nx.carry = 0;
-            cur = nxt;
-        }
-    }
+    int tile, sub, part, slot;
+    if (!raster_map_block<NQ>(A, (int)blockIdx.x, tile, sub, part, slot)) return;
+    raster_tile<CP, ColorT, AUX, NQ, PACKED, LISTS>(A, tile, sub, part, s_stage, slot, r_a, r_b, r_c, r_g);
 }
 
 // ---- clean-up pass of a lazily sorted frame -----------------------------------------------------
@@ -1416,26 +1261,6 @@ static int raster_parts_override() {
     return v;
 }
 
-// MOJOSPLAT_RASTER_HALF=1: one-quad waves keep a compacted stream per 8x4 half (A/B: profiles/r06_raster_halfquad.md)
-static bool raster_half() {
-    static const bool v = [] {
-        const char *e = getenv("MOJOSPLAT_RASTER_HALF");
-        return e && e[0] == '1';
-    }();
-    return v;
-}
-
-// MOJOSPLAT_RASTER_CHAIN=k: blocks a rasteriser wave walks one after the other (1: one block per wave, as rounds 2-5;
-// A/B: profiles/r06_raster_startup.md)
-static int raster_chain() {
-    static const int v = [] {
-        const char *e = getenv("MOJOSPLAT_RASTER_CHAIN");
-        const int k = e ? atoi(e) : 1;
-        return k >= 1 && k <= 16 ? k : 1;
-    }();
-    return v;
-}
-
 static unsigned redo_grid(const RasterArgs &A) { return (unsigned)(A.lazy.redo_grid >= 1 && A.lazy.redo_grid <= 4096 ? A.lazy.redo_grid : 64); }
 
 // The clean-up launches behind a lazily sorted frame's rasteriser: empty on almost every frame.
@@ -1488,41 +1313,7 @@ void launch_cp(const RasterArgs &A_in, hipStream_t stream, void *after_raster_ev
         else if (A.parts == 4) MS_LAUNCH_RASTER(AUXV, 1, PK);  \
         else MS_LAUNCH_RASTER(AUXV, 4, PK);                    \
     } while (0)
-    bool done = false;
-#if MS_RASTER_CHAINS   // (measurement builds, profiles/r06_raster_startup.md: -DMS_RASTER_CHAINS=1; never the shipped library)
     if constexpr (CP == 3) {
-        if (A.records && !aux && !A.quad_lists && A.order && !A.order_bins && (A.nsx == 1 || A.nsx == 2 || A.nsx == 4) && (raster_chain() > 1 || getenv("MOJOSPLAT_RASTER_CHAIN_KERNEL"))) {   // (the second: the chain kernel walking one block, to tell its code from its schedule)
-            // persistent waves (round 6): as many as the chip holds at once, each walking blocks index, index + grid, ...
-            RasterArgs P = A;
-            P.nvb = (int)grid.x;
-            // CHAINS of blocks: a wave walks `chain` blocks -- index, index + grid, ... with grid = indices / chain -- and the
-            // waves are still dispatched one by one as slots come free.  (All waves resident at once and each walking a
-            // fixed share of ALL blocks was measured first: the static shares end 25 % apart -- 125 us against 96 at
-            // config 3, resident waves falling from 60 % of the kernel on: profiles/r06_raster_startup.md.)
-            const int chain = raster_chain();
-            auto launch_p = [&](auto kernel, int parts) {
-                const int unit = 8 * parts;
-                int g = ((P.nvb + chain - 1) / chain + unit - 1) / unit * unit;
-                if (g <= 0) g = unit;
-                hipLaunchKernelGGL(kernel, dim3((unsigned)g), dim3(64), 0, stream, P);
-            };
-            if (A.parts == 2) launch_p(k_rasterize_fwd<CP, ColorT, false, 2, true, false, true>, 2);
-            else if (A.parts == 4) launch_p(k_rasterize_fwd<CP, ColorT, false, 1, true, false, true>, 4);
-            else launch_p(k_rasterize_fwd<CP, ColorT, false, 4, true, false, true>, 1);
-            done = true;
-        }
-    }
-#endif
-    if constexpr (CP == 3) {
-        if (done) {
-        } else
-#if MS_RASTER_HALF_STREAMS   // (measurement builds, profiles/r06_raster_halfquad.md: -DMS_RASTER_HALF_STREAMS=1 + MOJOSPLAT_RASTER_HALF=1)
-        if (A.records && !aux && !A.quad_lists && A.parts == 4 && raster_half()) {
-            // one quad a wave, its two halves walking streams of their own
-            hipLaunchKernelGGL((k_rasterize_fwd<CP, ColorT, false, 1, true, false, false, true>), grid, dim3(64), 0, stream, A);
-            done = true;
-        } else
-#endif
         if (A.records) {
             if (aux) MS_LAUNCH_RASTER_NQ(true, true);
             else if (A.quad_lists) {   // a differentiable frame that leaves its quads' lists for the backward
@@ -1531,10 +1322,9 @@ void launch_cp(const RasterArgs &A_in, hipStream_t stream, void *after_raster_ev
                 else hipLaunchKernelGGL((k_rasterize_fwd<CP, ColorT, false, 4, true, true>), grid, dim3(64), 0, stream, A);
             }
             else MS_LAUNCH_RASTER_NQ(false, true);
-            done = true;
         }
     }
-    if (!done) {
+    if (CP != 3 || !A.records) {
         if (aux) MS_LAUNCH_RASTER_NQ(true, false);
         else MS_LAUNCH_RASTER_NQ(false, false);
     }

@@ -49,12 +49,6 @@ constexpr int kTile = 8;       // entries per matrix tile (rows 0-7 of Y: vs, ro
 constexpr int kYStride = 68;   // floats per row of Y: the A fragments are read as ds_read_b128 at (row, 16 g + 4 i)
 constexpr int kRowQ = 16;      // floats per packed gradient row: gx gy s1 s2 s3 m0 c0 c1 c2 - ...
 constexpr int kSlots = kTile + kBatch + kGroup;
-#ifndef MS_BWDQ_ABLATE
-#define MS_BWDQ_ABLATE 0
-#endif
-#ifndef MS_BWDQ_PREFETCH
-#define MS_BWDQ_PREFETCH 0
-#endif
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -94,25 +88,15 @@ struct BwdQStage {
     float2 c[kSlots];               // b, Gaussian index (bits)
     __attribute__((aligned(16))) float y[16 * kYStride];
     __attribute__((aligned(16))) float e[kTile * 16];
-#ifdef MS_BWDQ_LDS_PAD   // (measurement builds: extra LDS per wave, to hold fewer waves per CU)
-    float pad[MS_BWDQ_LDS_PAD];
-#endif
 };
 
 // Every wave is a workgroup of its own and the LDS executes one wave's instructions in order: what a lane stores is there
 // for any lane's later load without a wait.  What is needed is that the COMPILER keeps the order (it reasons per lane and
-// would move a lane's load above another lane's store): a compiler barrier, no s_waitcnt (MS_BWDQ_FENCE=1: the fences of
-// the forward kernel's wave_lds_sync, for comparison).
+// would move a lane's load above another lane's store): a compiler barrier, no s_waitcnt.
 __device__ __forceinline__ void wave_lds_sync_q() {
-#if defined(MS_BWDQ_FENCE) && MS_BWDQ_FENCE
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-#else
     asm volatile("" ::: "memory");
     __builtin_amdgcn_wave_barrier();
     asm volatile("" ::: "memory");
-#endif
 }
 
 // One wave: quad `q` (0..3) of 16x16 block `sub` of tile `tile`.
@@ -228,10 +212,6 @@ __device__ __forceinline__ void bwd_quad(const BwdQArgs &A, const int tile, cons
 
     // the matrix tile -> sums -> rows.  n: entries of the tile (<= kTile), tbase: stream slot of the tile's entry 0
     auto fire = [&](const int n, const int tbase) __attribute__((always_inline)) {
-#if MS_BWDQ_ABLATE & 2   // (measurement builds: the walk alone)
-        if (n > 64) S.e[0] = 0.f;
-        return;
-#endif
         wave_lds_sync_q();
         const char *yb = reinterpret_cast<const char *>(S.y) + a_frag;
         u32x4 af[4];
@@ -257,9 +237,6 @@ __device__ __forceinline__ void bwd_quad(const BwdQArgs &A, const int tile, cons
             }
         }
         wave_lds_sync_q();
-#if MS_BWDQ_ABLATE & 4   // (measurement builds: the walk and the matrix instructions, no moment shift, no rows)
-        return;
-#endif
         // eight lanes move the entries' moments from the quad centre to the Gaussians' means (dx = u - x, dy = v - y) ...
         if (lane < n) {
             const float4 e0 = *reinterpret_cast<const float4 *>(S.e + lane * 16);
@@ -293,11 +270,7 @@ __device__ __forceinline__ void bwd_quad(const BwdQArgs &A, const int tile, cons
                     const float *row = S.e + slot * 16;
                     if (row[13] != 0.f) {
                         const unsigned gi = (unsigned)__float_as_int(row[12]);
-#if MS_BWDQ_ABLATE & 1   // (measurement builds: no global atomics)
-                        if (row[col] == 1.2345678e-30f) A.packed[(size_t)gi * kRowQ + col] = 1.f;
-#else
                         atomicAdd(reinterpret_cast<float *>(reinterpret_cast<char *>(A.packed) + (gi * (kRowQ * 4u) + (unsigned)col * 4u)), row[col]);
-#endif
                     }
                 }
             }
@@ -390,13 +363,8 @@ __device__ __forceinline__ void bwd_quad(const BwdQArgs &A, const int tile, cons
                     blue[j] = S.c[k + j].x;
                 }
             };
-#if MS_BWDQ_PREFETCH
-            if (n > 0) load_pair(kTile);
-#endif
             for (int k0 = kTile; k0 < kTile + n; k0 += kGroup) {
-#if !MS_BWDQ_PREFETCH
                 load_pair(k0);
-#endif
                 float alpha[kGroup], m[kGroup], v[kGroup], tin[kGroup], cd[kGroup];
                 bool clamped[kGroup];
 #pragma unroll
@@ -415,11 +383,6 @@ __device__ __forceinline__ void bwd_quad(const BwdQArgs &A, const int tile, cons
                     asm volatile("" : "+v"(m[j]));
                     cd[j] = fmaf(rb[j].z, vo[0], fmaf(rb[j].w, vo[1], blue[j] * vo[2]));
                 }
-#if MS_BWDQ_PREFETCH
-                // the record registers are free: the next pair's loads fly while this pair's chain runs (the slots behind
-                // the stream's end hold the neutral records or stale ones: never evaluated)
-                load_pair(min(k0 + kGroup, kSlots - kGroup));
-#endif
                 const float t_in = t;
 #pragma unroll
                 for (int j = 0; j < kGroup; ++j) {
