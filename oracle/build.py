@@ -16,10 +16,17 @@ def build(force: bool = False) -> str:
     os.makedirs(OUT_DIR, exist_ok=True)
     if not force and os.path.exists(OUT) and os.path.getmtime(OUT) >= os.path.getmtime(SRC):
         return OUT
+    # processes that start together (the spawned ranks of tests/test_distributed_cpu.py) may all build: each writes its
+    # own temporary file, and the rename puts one complete library in place atomically whichever finishes last
+    tmp = f"{OUT}.{os.getpid()}.tmp"
     cmd = ["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC",
-           "-o", OUT + ".tmp", SRC, "-lm"]
-    subprocess.check_call(cmd)
-    os.replace(OUT + ".tmp", OUT)
+           "-o", tmp, SRC, "-lm"]
+    try:
+        subprocess.check_call(cmd)
+        os.replace(tmp, OUT)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
     return OUT
 
 

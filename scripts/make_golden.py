@@ -9,7 +9,7 @@ inert placeholder module is registered under that name before the import.  Only 
 reference's pure-PyTorch functions are executed (project_gaussians(backend="torch"),
 bin_gaussians_to_tiles(backend="torch")); no Mojo / gsplat code path is touched.
 
-Usage: python scripts/make_golden.py
+Usage: python scripts/make_golden.py [--only NAME]   (--only: write that one case, leave the other files alone)
 """
 import os
 import sys
@@ -68,8 +68,36 @@ def scene_raster_tests(N, seed):
     return means3d, ls, quats, opac, colors
 
 
+def scene_general_camera(N, W, H, fx, fy, cx, cy, seed):
+    """A look_at view with fx != fy and an off-centre principal point; the Gaussians are placed in CAMERA space -- most
+    of them in view, a share past each of the four FOV-clamp limits (their Jacobian is clamped), a few culled -- and
+    mapped to world coordinates."""
+    from mojosplat_amd.utils import look_at
+    gen = torch.Generator().manual_seed(seed)
+    vm = look_at(torch.tensor([1.8, -1.2, -4.5]), torch.tensor([0.3, 0.2, 0.4]), torch.tensor([0.0, 1.0, 0.0]))
+    R, t = vm[:3, :3], vm[:3, 3]
+    z = torch.rand(N, generator=gen) * 5.0 + 2.5
+    sx = torch.rand(N, generator=gen) * 1.2 * W - 0.1 * W
+    sy = torch.rand(N, generator=gen) * 1.2 * H - 0.1 * H
+    u, v = (sx - cx) / fx, (sy - cy) / fy
+    lims = ((W - cx) / fx + 0.15 * W / fx, cx / fx + 0.15 * W / fx, (H - cy) / fy + 0.15 * H / fy, cy / fy + 0.15 * H / fy)
+    k = N // 10   # per side: u or v beyond the limit by 0.02 .. 0.2
+    d = torch.rand(4 * k, generator=gen) * 0.18 + 0.02
+    u[:k], u[k:2 * k] = lims[0] + d[:k], -lims[1] - d[k:2 * k]
+    v[2 * k:3 * k], v[3 * k:4 * k] = lims[2] + d[2 * k:3 * k], -lims[3] - d[3 * k:]
+    pc = torch.stack([u * z, v * z, z], -1)
+    pc[-10:, 2] = -pc[-10:, 2]                         # behind the camera
+    means3d = ((pc - t) @ R).float().contiguous()
+    scales = torch.log(torch.rand(N, 3, generator=gen) * 0.15 + 0.04)
+    scales[:4 * k] += 1.2                              # clamped Gaussians large enough to reach into the image
+    quats = torch.nn.functional.normalize(torch.randn(N, 4, generator=gen), p=2, dim=-1)
+    opac = torch.sigmoid(torch.randn(N, generator=gen) + 1.0)
+    return means3d, scales, quats, opac, R.contiguous(), t.contiguous()
+
+
 def main():
     from mojosplat_amd.scenes import randscene_v1
+    only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None
 
     rp, rb, ru = import_reference()
     os.makedirs(OUT, exist_ok=True)
@@ -97,6 +125,14 @@ def main():
                      cy=cam.cy, near=cam.near, far=cam.far)
     cases["randscene_n5000_640x360"] = (sc["means3d"], sc["scales"], sc["quats"],
                                         sc["opacities"], sc["features"], rcam)
+
+    W, H = 250, 170
+    m, s, q, o, R, t = scene_general_camera(800, W, H, 140.0, 112.0, 0.35 * W, 0.62 * H, seed=2024)
+    cases["general_cam_n800_250x170"] = (m, s, q, o, None, ru.Camera(R=R, T=t, H=H, W=W, fx=140.0, fy=112.0, cx=0.35 * W,
+                                                                       cy=0.62 * H, near=0.1, far=100.0))
+    if only is not None:
+        assert only in cases, f"--only: no case {only!r}"
+        cases = {only: cases[only]}
 
     for name, (m, s, q, o, c, cam) in cases.items():
         means2d, conics, depths, radii = rp.project_gaussians(m, s, q, o.view(-1, 1), cam,

@@ -71,6 +71,27 @@ def oracle_project(oracle, means3d, scales, quats, opac, cam, **kw):
                               far=cam.far, **kw)
 
 
+# ------------------------------------------------------------------ the projection parity bar
+def check_projection(hip_out, orc_out, max_flips=0):
+    m2, con, dep, rad = (np_(t) for t in hip_out)
+    om2, ocon, odep, orad = orc_out
+    flips = np.nonzero((rad != orad).any(1))[0]
+    assert len(flips) <= max_flips, f"{len(flips)} radius mismatches"
+    if len(flips):
+        # a flip is a +-1 px radius or a cull decision on the viewport edge
+        both = (rad[flips] > 0).all(1) & (orad[flips] > 0).all(1)
+        assert (np.abs(rad[flips][both] - orad[flips][both]) <= 1).all()
+    ok = np.ones(len(rad), bool)
+    ok[flips] = False
+    np.testing.assert_allclose(m2[ok], om2[ok], rtol=1e-5, atol=1e-4)
+    np.testing.assert_allclose(dep[ok], odep[ok], rtol=1e-6, atol=1e-6)
+    scale = np.abs(ocon[ok]).max(axis=1, keepdims=True) + 1e-30
+    assert np.max(np.abs(con[ok] - ocon[ok]) / scale, initial=0.0) < 2e-5
+    culled = ok & ~(orad > 0).all(1)
+    assert (m2[culled] == 0).all() and (con[culled] == 0).all() and (dep[culled] == 0).all()
+    return len(flips)
+
+
 # ------------------------------------------------------------------ the raster parity bar
 # North star: <= 1e-4 abs per pixel fp32 against the reference rasteriser
 # (reference tests/test_rasterization.py:110: atol = rtol = 1e-4).  Two fp32 implementations of the
@@ -164,3 +185,143 @@ def assert_grad_close(name, got, ref, rel=2e-3, elem_rel=None, floor=1e-3, elem_
         if elem_p999 is not None:
             assert st["elem_rel_p999"] <= elem_p999, f"{name}: 99.9th percentile of the per-element error > {elem_p999}: {st}"
     return st
+
+
+# ------------------------------------------------------------------ general pinhole cameras
+# fx != fy and an off-centre principal point: the FOV clamp's two sides differ (lim_pos != lim_neg) and any fx / fy swap
+# changes the numbers.  Scenes are placed in CAMERA space -- in view, past each of the four clamp limits with an extent
+# that still reaches the image (alive, clamped Jacobian), at the near / far planes, and culled -- then mapped to world.
+SIDES = ("x_pos", "x_neg", "y_pos", "y_neg")
+KINK = 1e-4     # a Gaussian within this of a limit (in x/z or y/z) sits on the clamp's kink: none is placed there
+
+
+def fov_limits(cam):
+    """The clamp limits on x/z and y/z (csrc/project_device.hpp make_proj_params, oracle/torch_oracle.py), float64."""
+    tx, ty = 0.5 * cam.W / cam.fx, 0.5 * cam.H / cam.fy
+    return dict(x_pos=(cam.W - cam.cx) / cam.fx + 0.3 * tx, x_neg=cam.cx / cam.fx + 0.3 * tx,
+                y_pos=(cam.H - cam.cy) / cam.fy + 0.3 * ty, y_neg=cam.cy / cam.fy + 0.3 * ty)
+
+
+def general_camera(W, H, fx, fy, cx, cy, *, near=0.5, far=30.0, eye=(1.8, -1.2, -4.5), target=(0.3, 0.2, 0.4),
+                   device="cpu"):
+    from mojosplat_amd.utils import look_at
+    vm = look_at(torch.tensor(eye), torch.tensor(target), torch.tensor([0.0, 1.0, 0.0]))
+    return Camera(R=vm[:3, :3].contiguous().to(device), T=vm[:3, 3].contiguous().to(device), H=H, W=W, fx=fx, fy=fy,
+                  cx=cx, cy=cy, near=near, far=far)
+
+
+# name -> (W, H, fx, fy, cx, cy, near, far, axes whose principal point is off-centre)
+GENERAL_CAMERAS = {
+    "fx>fy_pp_xy": (330, 190, 300.0, 240.0, 0.35 * 330, 0.62 * 190, 0.5, 30.0, "xy"),
+    "fy>fx_pp_x": (330, 190, 240.0, 300.0, 0.68 * 330, 95.0, 0.5, 30.0, "x"),
+    "fx>fy_pp_y": (330, 190, 280.0, 224.0, 165.0, 0.3 * 190, 0.5, 30.0, "y"),
+    "fy>fx_pp_xy": (330, 190, 230.0, 287.5, 0.7 * 330, 0.33 * 190, 0.5, 30.0, "xy"),
+    "crop_cx<0": (330, 190, 300.0, 240.0, -0.25 * 330, 0.7 * 190, 0.5, 30.0, "xy"),
+    "crop_cy>H": (330, 190, 240.0, 300.0, 0.3 * 330, 1.3 * 190, 0.5, 30.0, "xy"),
+    "near2_far7": (330, 190, 300.0, 240.0, 0.38 * 330, 0.67 * 190, 2.0, 7.0, "xy"),
+}
+
+
+def camera_by_name(name, device="cpu", **kw):
+    W, H, fx, fy, cx, cy, near, far, _ = GENERAL_CAMERAS[name]
+    return general_camera(W, H, fx, fy, cx, cy, near=near, far=far, device=device, **kw)
+
+
+def assert_general_camera(cam, axes="xy"):
+    """The camera is not the centred, square one: |fx/fy - 1| >= 0.2 and, on every axis in `axes`, the two clamp limits
+    differ by at least 30 % of the larger one."""
+    assert abs(cam.fx / cam.fy - 1.0) >= 0.2 - 1e-9, (cam.fx, cam.fy)
+    L = fov_limits(cam)
+    for a in axes:
+        p, n = L[a + "_pos"], L[a + "_neg"]
+        assert abs(p - n) >= 0.3 * max(abs(p), abs(n)), (a, p, n)
+
+
+def general_scene(cam, *, n_view=1200, n_side=40, n_plane=24, n_cull=24, seed=0, channels=3, z_range=None,
+                  view_scale=(0.015, 0.1)):
+    """-> dict(means3d, scales, quats, opacities, features) (float32, CPU) and `kind` (N,) int: 0 in view, 1..4 past
+    SIDES[k - 1], 5 at the near / far plane, 6 culled (behind the camera, far off-screen, opacity < 1/255).
+    A side Gaussian sits 0.01 .. 0.1 past its limit (its centre 0.15 W + fx d beyond the image's edge) and is isotropic
+    with a footprint 1.1 .. 1.7 times that distance: its extent reaches into the image.  z_range (in-view depths):
+    default 2.5 .. 8, or half the near plane .. 1.3 x the far plane when near >= 1 (the planes cut through the scene)."""
+    if z_range is None:
+        z_range = (2.5, 8.0) if cam.near < 1.0 else (0.5 * cam.near, 1.3 * cam.far)
+    g = torch.Generator().manual_seed(seed)
+    rnd = lambda n, lo, hi: torch.rand(n, generator=g, dtype=torch.float64) * (hi - lo) + lo
+    W, H, fx, fy, cx, cy = cam.W, cam.H, cam.fx, cam.fy, cam.cx, cam.cy
+    L = fov_limits(cam)
+    parts, kinds, sc, op = [], [], [], []
+
+    def add(u, v, z, s, o, k):
+        parts.append(torch.stack([u * z, v * z, z], -1))
+        sc.append(s)
+        op.append(o)
+        kinds.append(torch.full((len(z),), k, dtype=torch.int64))
+
+    # in view: centres over the image and a margin of 0.1 W / 0.1 H (the limits sit 0.15 W / H out)
+    z = rnd(n_view, *z_range)
+    add((rnd(n_view, -0.1 * W, 1.1 * W) - cx) / fx, (rnd(n_view, -0.1 * H, 1.1 * H) - cy) / fy, z,
+        torch.exp(rnd(n_view, np.log(view_scale[0]), np.log(view_scale[1]))), rnd(n_view, 0.2, 0.95), 0)
+    # past each limit
+    for k, side in enumerate(SIDES):
+        d = rnd(n_side, 0.01, 0.1)
+        z = rnd(n_side, 2.5, 6.0)
+        o = rnd(n_side, 0.3, 0.8)
+        ext = torch.sqrt(2.0 * torch.log(255.0 * o))
+        if side[0] == "x":
+            f, span, lim = fx, W, L[side]
+            u = lim + d if side == "x_pos" else -lim - d
+            v = (rnd(n_side, 0.1 * H, 0.9 * H) - cy) / fy
+        else:
+            f, span, lim = fy, H, L[side]
+            v = lim + d if side == "y_pos" else -lim - d
+            u = (rnd(n_side, 0.1 * W, 0.9 * W) - cx) / fx
+        dist = 0.15 * span + f * d
+        s = rnd(n_side, 1.1, 1.7) * dist * z / (ext * f * np.sqrt(1.0 + lim * lim))
+        add(u, v, z, s, o, 1 + k)
+    # at the planes: just in front of / behind the near plane and the far plane
+    h = n_plane // 2
+    zn = cam.near * torch.cat([rnd(h // 2, 0.9, 0.99), rnd(h - h // 2, 1.01, 1.1)])
+    zf = cam.far * torch.cat([rnd(h // 2, 0.98, 0.999), rnd(h - h // 2, 1.001, 1.02)])
+    z = torch.cat([zn, zf])
+    sig = rnd(n_plane, 1.5, 4.0)   # px
+    add((rnd(n_plane, 0.1 * W, 0.9 * W) - cx) / fx, (rnd(n_plane, 0.1 * H, 0.9 * H) - cy) / fy, z, sig * z / fx,
+        rnd(n_plane, 0.4, 0.9), 5)
+    # culled: behind the camera, far off-screen, nearly transparent
+    c3 = n_cull // 3
+    z = rnd(n_cull, 2.5, 6.0)
+    z[:c3] = -z[:c3]
+    u = (rnd(n_cull, 0.2 * W, 0.8 * W) - cx) / fx
+    u[c3:2 * c3] = 4.0 * (L["x_pos"] + 1.0)
+    o = rnd(n_cull, 0.3, 0.9)
+    o[2 * c3:] = 0.002
+    add(u, (rnd(n_cull, 0.2 * H, 0.8 * H) - cy) / fy, z, rnd(n_cull, 0.03, 0.08), o, 6)
+
+    pc = torch.cat(parts)
+    N = pc.shape[0]
+    R, t = cam.R.detach().cpu().double(), cam.T.detach().cpu().double()
+    means3d = ((pc - t) @ R).float().contiguous()
+    s = torch.cat(sc)
+    kind = torch.cat(kinds)
+    iso = (kind >= 1) & (kind <= 4)
+    scales = torch.log(s)[:, None].repeat(1, 3) + torch.where(iso[:, None], 0.0, 0.3 * torch.randn(N, 3, generator=g, dtype=torch.float64))
+    quats = torch.nn.functional.normalize(torch.randn(N, 4, generator=g), dim=1)
+    scene = dict(means3d=means3d, scales=scales.float().contiguous(), quats=quats.contiguous(),
+                 opacities=torch.cat(op).float().contiguous(), features=torch.rand(N, channels, generator=g).contiguous())
+    return scene, kind
+
+
+def clamp_counts(means3d, cam, alive):
+    """Alive Gaussians whose x/z or y/z lies beyond each limit by more than KINK (float64) -> dict side -> count, and
+    the mask of Gaussians within KINK of any limit."""
+    m = torch.as_tensor(np.asarray(np_(means3d) if torch.is_tensor(means3d) else means3d), dtype=torch.float64)
+    vm = cam.view_matrix.detach().cpu().double()
+    pc = m @ vm[:3, :3].T + vm[:3, 3]
+    u, v = (pc[:, 0] / pc[:, 2]).numpy(), (pc[:, 1] / pc[:, 2]).numpy()
+    L = fov_limits(cam)
+    alive = np.asarray(np_(alive) if torch.is_tensor(alive) else alive, bool)
+    past = dict(x_pos=u > L["x_pos"] + KINK, x_neg=u < -L["x_neg"] - KINK, y_pos=v > L["y_pos"] + KINK,
+                y_neg=v < -L["y_neg"] - KINK)
+    kink = (np.abs(u - L["x_pos"]) <= KINK) | (np.abs(u + L["x_neg"]) <= KINK) | (np.abs(v - L["y_pos"]) <= KINK) | \
+        (np.abs(v + L["y_neg"]) <= KINK)
+    return {k: int((alive & p).sum()) for k, p in past.items()}, kink

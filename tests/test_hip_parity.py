@@ -18,33 +18,13 @@ import torch
 
 import mojosplat_amd as ms
 import oracle
-from helpers import (camera_from_golden, check_image_strict, golden_files, load_golden, np_, oracle_project,
-                     proj_scene, raster_scene, simple_camera)
+from helpers import (camera_from_golden, check_image_strict, check_projection, golden_files, load_golden, np_,
+                     oracle_project, proj_scene, raster_scene, simple_camera)
 from mojosplat_amd.binning import bin_gaussians_to_tiles_hip, isect_offset_encode_hip
 from mojosplat_amd.rasterization import rasterize_gaussians_hip
 from mojosplat_amd.scenes import BACKGROUND_V1, randscene_v1
 
 pytestmark = pytest.mark.gpu
-
-
-def check_projection(hip_out, orc_out, max_flips=0):
-    m2, con, dep, rad = (np_(t) for t in hip_out)
-    om2, ocon, odep, orad = orc_out
-    flips = np.nonzero((rad != orad).any(1))[0]
-    assert len(flips) <= max_flips, f"{len(flips)} radius mismatches"
-    if len(flips):
-        # a flip is a +-1 px radius or a cull decision on the viewport edge
-        both = (rad[flips] > 0).all(1) & (orad[flips] > 0).all(1)
-        assert (np.abs(rad[flips][both] - orad[flips][both]) <= 1).all()
-    ok = np.ones(len(rad), bool)
-    ok[flips] = False
-    np.testing.assert_allclose(m2[ok], om2[ok], rtol=1e-5, atol=1e-4)
-    np.testing.assert_allclose(dep[ok], odep[ok], rtol=1e-6, atol=1e-6)
-    scale = np.abs(ocon[ok]).max(axis=1, keepdims=True) + 1e-30
-    assert np.max(np.abs(con[ok] - ocon[ok]) / scale, initial=0.0) < 2e-5
-    culled = ok & ~(orad > 0).all(1)
-    assert (m2[culled] == 0).all() and (con[culled] == 0).all() and (dep[culled] == 0).all()
-    return len(flips)
 
 
 def check_image(img, ref, atol=1e-4, max_outlier_frac=2e-4, outlier_cap=2e-2):
