@@ -21,6 +21,8 @@
  *   ms_render_bwd                     the backward of such a frame (no reference counterpart) in one call
  *   ms_render_bwd_finish_densify,     3DGS densification statistics accumulated in a training backward
  *   ms_densify_stats_update           (no reference counterpart)
+ *   ms_*_pose, ms_pose_scratch_bytes  the gradient w.r.t. the camera pose (view matrix / camera centre) in the
+ *                                     training backward (no reference counterpart; gsplat returns it)
  *   ms_render_fwd_batch               the same for C cameras: the camera dimension of the reference's
  *                                     kernels (kernels/projection.mojo:32-37) that its wrappers pin to 1
  *
@@ -54,7 +56,8 @@
 extern "C" {
 #endif
 
-#define MS_ABI_VERSION 3   /* 2: ms_render_bwd takes the frame's image (render_colors); 3: ms_render_redo_counts, the band-frame pair, ms_scene_prepare */
+#define MS_ABI_VERSION 4   /* 2: ms_render_bwd takes the frame's image (render_colors); 3: ms_render_redo_counts, the band-frame pair, ms_scene_prepare;
+                              4: the pose-gradient entry points (ms_pose_scratch_bytes, ms_*_pose) */
 
 typedef enum ms_status {
     MS_OK = 0,
@@ -316,6 +319,54 @@ int ms_render_bwd(int64_t N, const float *means3d, const float *scales, int scal
                   const int32_t *last_ids, const float *v_render_colors, const float *v_render_alphas, float *v_means3d,
                   float *v_scales, float *v_quats, float *v_opacities, float *v_colors, void *bwd_workspace,
                   size_t bwd_workspace_bytes, void *mid_event, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Gradients w.r.t. the camera pose (pose refinement, SLAM-style tracking, bundle-adjusting 3DGS; gsplat's v_viewmats).
+ * Each entry point below is its namesake above with three more arguments before `stream`, and computes exactly what its
+ * namesake computes -- every other output bit for bit, the densification statistics included -- plus:
+ *   v_viewmat f32[16] (ms_project_gaussians_bwd_pose, ms_render_bwd_finish_pose, ms_render_bwd_finish_densify_pose,
+ *     ms_render_bwd_pose): dL/d(viewmat), the row-major world->camera [R | t; 0 0 0 1] the call was given -- through the
+ *     camera-space means (p_c = R p + t) and covariances (R Sigma R^T) of the Gaussians the backward differentiates;
+ *     OVERWRITTEN, bottom row 0.
+ *   v_campos f32[3] (ms_spherical_harmonics_bwd_pose): dL/d(cam_x, cam_y, cam_z) through the viewing directions;
+ *     OVERWRITTEN.  (The camera centre is -R^T t; the caller chains it into the view matrix.)
+ *   pose_scratch: ms_pose_scratch_bytes(N) bytes, 16-byte aligned, caller-owned: one 64-byte partial sum per workgroup
+ *     of 256 Gaussians, written by the backward kernel and summed by a one-workgroup launch behind it (no atomics).
+ *     Its contents are garbage before and after the call.
+ * The sum runs in an order that depends on N alone: the result is bitwise reproducible from run to run.
+ * v_viewmat / v_campos NULL: exactly the namesake's work (the scratch is not touched and may be NULL).  N == 0 or an
+ * empty frame: zeros.  No reference counterpart (the reference is forward-only: render.py:11). */
+size_t ms_pose_scratch_bytes(int64_t N);
+int ms_project_gaussians_bwd_pose(int64_t N, const float *means3d, const float *scales, int scales_are_log,
+                                  const float *quats, const float *viewmat, float fx, float fy, float cx, float cy, int W,
+                                  int H, float eps2d, const int32_t *radii, const float *v_means2d, const float *v_conics,
+                                  const float *v_depths, float *v_means3d, float *v_scales, float *v_quats,
+                                  float *v_viewmat, void *pose_scratch, size_t pose_scratch_bytes, void *stream);
+int ms_render_bwd_finish_pose(int64_t N, const float *means3d, const float *scales, int scales_are_log, const float *quats,
+                              const float *opacities, int CDIM, const float *viewmat, float fx, float fy, float cx, float cy,
+                              int W, int H, float eps2d, const float *rows, float *v_means3d, float *v_scales, float *v_quats,
+                              float *v_opacities, float *v_colors, float *v_viewmat, void *pose_scratch,
+                              size_t pose_scratch_bytes, void *stream);
+int ms_render_bwd_finish_densify_pose(int64_t N, const float *means3d, const float *scales, int scales_are_log,
+                                      const float *quats, const float *opacities, int CDIM, const float *viewmat, float fx,
+                                      float fy, float cx, float cy, int W, int H, float eps2d, const float *rows,
+                                      float *v_means3d, float *v_scales, float *v_quats, float *v_opacities,
+                                      float *v_colors, float near_plane, float far_plane, float *grad2d, float *count,
+                                      float *max_radii, float *v_viewmat, void *pose_scratch, size_t pose_scratch_bytes,
+                                      void *stream);
+int ms_render_bwd_pose(int64_t N, const float *means3d, const float *scales, int scales_are_log, const float *quats,
+                       const float *opacities, const float *colors, int CDIM, const float *viewmat, float fx, float fy,
+                       float cx, float cy, int W, int H, float eps2d, int tile_size, const float *backgrounds,
+                       const void *workspace, size_t workspace_bytes, const void *isect_buf, size_t isect_bytes,
+                       const int64_t *host_info, const float *render_colors, const float *render_alphas,
+                       const int32_t *last_ids, const float *v_render_colors, const float *v_render_alphas,
+                       float *v_means3d, float *v_scales, float *v_quats, float *v_opacities, float *v_colors,
+                       void *bwd_workspace, size_t bwd_workspace_bytes, void *mid_event, float *v_viewmat,
+                       void *pose_scratch, size_t pose_scratch_bytes, void *stream);
+int ms_spherical_harmonics_bwd_pose(int64_t N, int K, int degree, const float *means3d, float cam_x, float cam_y,
+                                    float cam_z, const float *coeffs, const int32_t *radii, int add_half_and_clamp,
+                                    const float *colors_fwd, const float *v_colors, float *v_coeffs, float *v_means3d,
+                                    float *v_campos, void *pose_scratch, size_t pose_scratch_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Spherical-harmonic colours (view dependent).  The reference leaves SH evaluation as a TODO

@@ -18,7 +18,7 @@ _LIB_PATH = os.environ.get("MOJOSPLAT_HIP_LIB") or \
     os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libmojosplat_hip.so")
 _lib = None
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 # name -> (restype, argtypes); mirrors include/mojosplat_hip.h one to one
 _SIGNATURES = {
@@ -123,6 +123,12 @@ _SIGNATURES["ms_render_bwd_finish_densify"] = (c_int, [c_int64, c_void_p, c_void
                                                        c_float, c_float, c_float, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
                                                        c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p,
                                                        c_void_p])
+# the pose-gradient twins (include/mojosplat_hip.h): the namesake's arguments, then v_viewmat / v_campos, scratch, its bytes
+_SIGNATURES["ms_pose_scratch_bytes"] = (c_size_t, [c_int64])
+for _name in ("ms_project_gaussians_bwd", "ms_render_bwd_finish", "ms_render_bwd_finish_densify", "ms_render_bwd",
+              "ms_spherical_harmonics_bwd"):
+    _r, _a = _SIGNATURES[_name]
+    _SIGNATURES[_name + "_pose"] = (_r, _a[:-1] + [c_void_p, c_void_p, c_size_t, c_void_p])
 _SIGNATURES["ms_densify_stats_update"] = (c_int, [c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
 _SIGNATURES["ms_scene_block_bounds_bytes"] = (c_size_t, [c_int64, c_int])
 _SIGNATURES["ms_scene_prepare"] = (c_int, [c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p])

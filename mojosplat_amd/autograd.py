@@ -24,14 +24,27 @@ from .rasterization import rasterize_gaussians_hip
 from .utils import Camera
 
 
+def _pose_out(L, N, dev):
+    """dL/dviewmat f32[16] and its scratch (include/mojosplat_hip.h, ms_pose_scratch_bytes): both overwritten by the call."""
+    return (torch.empty(16, dtype=torch.float32, device=dev),
+            torch.empty(L.ms_pose_scratch_bytes(N), dtype=torch.uint8, device=dev))
+
+
+def _pose_grad(v_vm, meta):
+    """v_viewmat f32[16] -> the (4, 4) gradient in the view matrix's own dtype and device (meta)."""
+    return v_vm.view(4, 4).to(device=meta[1], dtype=meta[0])
+
+
 class _ProjectHip(torch.autograd.Function):
+    # viewmat: camera.view_matrix as an input of its own -- its gradient (the camera pose) comes back when it requires one
     @staticmethod
-    def forward(ctx, means3d, scales, quats, opacities, camera, densify=None):
+    def forward(ctx, means3d, scales, quats, opacities, camera, densify=None, viewmat=None):
         means3d, scales, quats = _hip.f32c(means3d), _hip.f32c(scales), _hip.f32c(quats)
         out = project_gaussians_hip(means3d, scales, quats, opacities, camera)
         means2d, conics, depths, radii = out
         ctx.camera = camera
         ctx.densify = densify   # (DensifyStats: updated by the first backward only)
+        ctx.vm_meta = None if viewmat is None else (viewmat.dtype, viewmat.device)
         ctx.save_for_backward(means3d, scales, quats, radii)
         ctx.mark_non_differentiable(radii)
         return means2d, conics, depths, radii
@@ -50,18 +63,28 @@ class _ProjectHip(torch.autograd.Function):
         v_scales = torch.empty((N, 3), dtype=torch.float32, device=dev)
         v_quats = torch.empty((N, 4), dtype=torch.float32, device=dev)
         vm = cam._viewmat_f32().to(dev)
+        pose = ctx.vm_meta is not None and ctx.needs_input_grad[6]
         with torch.cuda.device(dev):
-            _hip.check(L.ms_project_gaussians_bwd(
-                N, _hip.ptr(means3d), _hip.ptr(scales), 1, _hip.ptr(quats), _hip.ptr(vm), cam.fx,
-                cam.fy, cam.cx, cam.cy, cam.W, cam.H, EPS2D, _hip.ptr(radii), _hip.ptr(v_means2d),
-                _hip.ptr(v_conics), _hip.ptr(v_depths), _hip.ptr(v_means3d), _hip.ptr(v_scales),
-                _hip.ptr(v_quats), _hip.stream(dev)), "ms_project_gaussians_bwd")
+            if pose:
+                v_vm, pws = _pose_out(L, N, dev)
+                _hip.check(L.ms_project_gaussians_bwd_pose(
+                    N, _hip.ptr(means3d), _hip.ptr(scales), 1, _hip.ptr(quats), _hip.ptr(vm), cam.fx,
+                    cam.fy, cam.cx, cam.cy, cam.W, cam.H, EPS2D, _hip.ptr(radii), _hip.ptr(v_means2d),
+                    _hip.ptr(v_conics), _hip.ptr(v_depths), _hip.ptr(v_means3d), _hip.ptr(v_scales),
+                    _hip.ptr(v_quats), _hip.ptr(v_vm), _hip.ptr(pws), pws.numel(), _hip.stream(dev)),
+                    "ms_project_gaussians_bwd_pose")
+            else:
+                _hip.check(L.ms_project_gaussians_bwd(
+                    N, _hip.ptr(means3d), _hip.ptr(scales), 1, _hip.ptr(quats), _hip.ptr(vm), cam.fx,
+                    cam.fy, cam.cx, cam.cy, cam.W, cam.H, EPS2D, _hip.ptr(radii), _hip.ptr(v_means2d),
+                    _hip.ptr(v_conics), _hip.ptr(v_depths), _hip.ptr(v_means3d), _hip.ptr(v_scales),
+                    _hip.ptr(v_quats), _hip.stream(dev)), "ms_project_gaussians_bwd")
             if ctx.densify is not None:
                 st, ctx.densify = ctx.densify, None
                 _hip.check(L.ms_densify_stats_update(N, cam.W, cam.H, _hip.ptr(radii), _hip.ptr(v_means2d), _hip.ptr(st.grad2d),
                                                      _hip.ptr(st.count), _hip.ptr(st.max_radii), _hip.stream(dev)),
                            "ms_densify_stats_update")
-        return v_means3d, v_scales, v_quats, None, None, None
+        return v_means3d, v_scales, v_quats, None, None, None, _pose_grad(v_vm, ctx.vm_meta) if pose else None
 
 
 class _RasterizeHip(torch.autograd.Function):
@@ -116,7 +139,7 @@ class _RenderFusedHip(torch.autograd.Function):
     rasterise -- the inference path's forward -- with the frame's scratch kept alive for backward."""
 
     @staticmethod
-    def forward(ctx, means3d, scales, quats, opacities, colors, background, camera, tile_size, densify=None):
+    def forward(ctx, means3d, scales, quats, opacities, colors, background, camera, tile_size, densify=None, viewmat=None):
         from ._fused import WHOLE, _Frame
         from . import render as _render   # bench.py's in-situ stage timing hook (None otherwise)
         evs = _render._STAGE_HOOK() if _render._STAGE_HOOK is not None else None
@@ -143,6 +166,8 @@ class _RenderFusedHip(torch.autograd.Function):
             _render._settle(key, tile_size, _render.bin_rule(tile_size, M, info["on_grid"], camera.W, camera.H, grid_px=tile_size))
         ctx.empty = info["on_grid"] == 0
         ctx.camera, ctx.tile_size = camera, tile_size
+        # (viewmat: camera.view_matrix as an input of its own, for the gradient w.r.t. the camera pose)
+        ctx.vm_meta = None if viewmat is None else (viewmat.dtype, viewmat.device)
         # (DensifyStats of a lean frame: the first backward's finish updates them; an empty frame has nothing alive)
         ctx.densify = densify if lean else None
         m3, sc, qu, op, col, bg = frame.keep[:6]
@@ -163,10 +188,12 @@ class _RenderFusedHip(torch.autograd.Function):
     @staticmethod
     def backward(ctx, v_img):
         cam, ts = ctx.camera, ctx.tile_size
+        pose = ctx.vm_meta is not None and ctx.needs_input_grad[9]
         if ctx.empty:
             m3, sc, qu, op, col, bg = ctx.saved_tensors
             return (torch.zeros_like(m3), torch.zeros_like(sc), torch.zeros_like(qu), torch.zeros_like(op),
-                    torch.zeros_like(col), None if bg is None else torch.zeros_like(bg), None, None, None)
+                    torch.zeros_like(col), None if bg is None else torch.zeros_like(bg), None, None, None,
+                    torch.zeros(4, 4, dtype=ctx.vm_meta[0], device=ctx.vm_meta[1]) if pose else None)
         m3, sc, qu, op, col, bg, alphas, last, img = ctx.saved_tensors
         ws, isect, host = ctx.scratch
         L = _hip.lib()
@@ -182,6 +209,9 @@ class _RenderFusedHip(torch.autograd.Function):
         bws_bytes = L.ms_render_bwd_workspace_bytes(N, C)
         bws = None if rows_in_ws else torch.empty(bws_bytes, dtype=torch.uint8, device=dev)
         vm = cam._viewmat_f32().to(dev)
+        # (the camera pose: the *_pose twins of the calls below, with v_viewmat and its scratch; NULL-free only when asked)
+        v_vm, pws = _pose_out(L, N, dev) if pose else (None, None)
+        pose_args = (_hip.ptr(v_vm), _hip.ptr(pws), pws.numel()) if pose else ()
         bev = _BWD_HOOK() if _BWD_HOOK is not None else None
         with _hip.on_device(dev):
             if bev:
@@ -212,17 +242,19 @@ class _RenderFusedHip(torch.autograd.Function):
                 if bev:
                     bev[1].record()
                 if ctx.densify is None:
-                    _hip.check(L.ms_render_bwd_finish(N, _hip.ptr(m3), _hip.ptr(sc), 1, _hip.ptr(qu), _hip.ptr(op), 3, _hip.ptr(vm), cam.fx,
-                                                      cam.fy, cam.cx, cam.cy, cam.W, cam.H, EPS2D, _hip.ptr(rows), _hip.ptr(v_means3d),
-                                                      _hip.ptr(v_scales), _hip.ptr(v_quats), _hip.ptr(v_opac), _hip.ptr(v_colors),
-                                                      _hip.stream(dev)), "ms_render_bwd_finish")
+                    fn = L.ms_render_bwd_finish_pose if pose else L.ms_render_bwd_finish
+                    _hip.check(fn(N, _hip.ptr(m3), _hip.ptr(sc), 1, _hip.ptr(qu), _hip.ptr(op), 3, _hip.ptr(vm), cam.fx,
+                                  cam.fy, cam.cx, cam.cy, cam.W, cam.H, EPS2D, _hip.ptr(rows), _hip.ptr(v_means3d),
+                                  _hip.ptr(v_scales), _hip.ptr(v_quats), _hip.ptr(v_opac), _hip.ptr(v_colors), *pose_args,
+                                  _hip.stream(dev)), "ms_render_bwd_finish")
                 else:   # the same finish, also updating the densification statistics -- once per frame (retain_graph)
                     dst, ctx.densify = ctx.densify, None
-                    _hip.check(L.ms_render_bwd_finish_densify(
+                    fn = L.ms_render_bwd_finish_densify_pose if pose else L.ms_render_bwd_finish_densify
+                    _hip.check(fn(
                         N, _hip.ptr(m3), _hip.ptr(sc), 1, _hip.ptr(qu), _hip.ptr(op), 3, _hip.ptr(vm), cam.fx, cam.fy, cam.cx, cam.cy,
                         cam.W, cam.H, EPS2D, _hip.ptr(rows), _hip.ptr(v_means3d), _hip.ptr(v_scales), _hip.ptr(v_quats), _hip.ptr(v_opac),
                         _hip.ptr(v_colors), cam.near, cam.far, _hip.ptr(dst.grad2d), _hip.ptr(dst.count), _hip.ptr(dst.max_radii),
-                        _hip.stream(dev)), "ms_render_bwd_finish_densify")
+                        *pose_args, _hip.stream(dev)), "ms_render_bwd_finish_densify")
                 if bev:
                     bev[2].record()
                 if fronts:
@@ -231,25 +263,26 @@ class _RenderFusedHip(torch.autograd.Function):
             # projection, on the scratch the forward call left behind
             else:
               assert ctx.densify is None, "densification statistics are updated on lean frames only"
-              _hip.check(L.ms_render_bwd(
+              _hip.check((L.ms_render_bwd_pose if pose else L.ms_render_bwd)(
                 N, _hip.ptr(m3), _hip.ptr(sc), 1, _hip.ptr(qu), _hip.ptr(op), _hip.ptr(col), C, _hip.ptr(vm), cam.fx, cam.fy,
                 cam.cx, cam.cy, cam.W, cam.H, EPS2D, ts, _hip.ptr(bg), _hip.ptr(ws), ws.numel(), _hip.ptr(isect),
                 0 if isect is None else isect.numel(), host.ctypes.data, _hip.ptr(img) if C == 3 else None, _hip.ptr(alphas),
                 _hip.ptr(last), _hip.ptr(v_img),
                 None, _hip.ptr(v_means3d), _hip.ptr(v_scales), _hip.ptr(v_quats), _hip.ptr(v_opac), _hip.ptr(v_colors),
-                _hip.ptr(bws), bws_bytes, ctypes.c_void_p(bev[1].cuda_event) if bev else None, _hip.stream(dev)),
+                _hip.ptr(bws), bws_bytes, ctypes.c_void_p(bev[1].cuda_event) if bev else None, *pose_args, _hip.stream(dev)),
                 "ms_render_bwd")
               if bev:
                 bev[2].record()
         v_bg = None
         if bg is not None and ctx.needs_input_grad[5]:
             v_bg = ((1.0 - alphas)[..., None] * v_img).sum(dim=(0, 1))
-        return v_means3d, v_scales, v_quats, v_opac, v_colors, v_bg, None, None, None
+        return v_means3d, v_scales, v_quats, v_opac, v_colors, v_bg, None, None, None, _pose_grad(v_vm, ctx.vm_meta) if pose else None
 
 
 def project_gaussians_autograd(means3d, scales, quats, opacities, camera: Camera, densify=None):
-    """densify: a DensifyStats (densify.py) that the backward updates with its v_means2d and this forward's radii."""
-    return _ProjectHip.apply(means3d, scales, quats, opacities, camera, densify)
+    """densify: a DensifyStats (densify.py) that the backward updates with its v_means2d and this forward's radii.
+    Differentiable w.r.t. camera.view_matrix too (the camera pose) when it requires grad."""
+    return _ProjectHip.apply(means3d, scales, quats, opacities, camera, densify, camera.view_matrix)
 
 
 def rasterize_gaussians_autograd(means2d, conics, colors, opacities, background, tile_ranges,
@@ -264,7 +297,9 @@ def render_gaussians_trainable(means3d, scales, quats, opacities, features, came
     """Differentiable twin of ``render_gaussians(backend="hip")``: grads for means3d, scales
     (log-space), quats, opacities and colours (BASELINE config 3).  With ``sh_degree`` and
     features of shape (N, K, 3) the colours are view-dependent SH (sh.py): gradients then reach
-    the coefficients and, through the viewing direction, the means.
+    the coefficients and, through the viewing direction, the means.  A ``camera.view_matrix`` that
+    requires grad gets the gradient w.r.t. the camera pose (projection, and the SH viewing
+    directions through the camera centre), on every route.
 
     The forward is the inference path's single library call (fused projection + counting, tight
     binning, sync-free emit + rasterise) with the backward's per-pixel records switched on;
@@ -304,6 +339,9 @@ def render_gaussians_trainable(means3d, scales, quats, opacities, features, came
             ids, ranges = bin_gaussians_to_tiles_hip(means2d, radii, depths, tile_size, tw, th)
         if ids.numel() == 0:
             # same zeros image as the inference path (reference render.py:73-76), grad-connected
-            return (means3d.sum() + features.sum()) * 0 + torch.zeros(camera.H, camera.W, C, device=dev)
+            img = (means3d.sum() + features.sum()) * 0 + torch.zeros(camera.H, camera.W, C, device=dev)
+            vm = camera.view_matrix
+            return img + vm.sum().to(dev) * 0 if vm.requires_grad else img
         return rasterize_gaussians_autograd(means2d, conics, features, opacities, bg, ranges, ids, camera, tile_size)
-    return _RenderFusedHip.apply(means3d, scales, quats, opacities.reshape(-1), features, bg, camera, bin_px, densify)
+    return _RenderFusedHip.apply(means3d, scales, quats, opacities.reshape(-1), features, bg, camera, bin_px, densify,
+                                 camera.view_matrix)

@@ -148,7 +148,11 @@ int project_bwd_from_rows(int64_t N, const float *means3d, const float *scales, 
                           const float *viewmat, float fx, float fy, float cx, float cy, int W, int H, float eps2d,
                           const int32_t *radii, const float *rows, int CDIM, float *v_means3d, float *v_scales,
                           float *v_quats, float *v_colors, float *v_opacities, void *stream,
-                          const float *raw_rows_opacities = nullptr);   // non-null: rasterize_bwdq.hip's raw sums (radii may be null)
+                          const float *raw_rows_opacities = nullptr,    // non-null: rasterize_bwdq.hip's raw sums (radii may be null)
+                          // non-null: dL/dviewmat f32[16] (overwritten, bottom row 0) through ms_pose_scratch_bytes(N) of scratch
+                          float *v_viewmat = nullptr, void *pose_scratch = nullptr);
+// project_bwd.hip: the checks of a pose-gradient entry point's output and scratch (ms_pose_scratch_bytes)
+int check_pose_out(int64_t N, const float *out, const void *scratch, size_t scratch_bytes, const char *who);
 void isect_lazy_arrays(void *workspace, int64_t N, int tile_w, int tile_h, LazyLists *out);
 bool depth_cut_fits(int64_t N, int tile_w, int tile_h);
 // lazily sorted fronts: depth (entries) of a front, LDS room for it, depth buckets from the camera planes

@@ -749,30 +749,57 @@ extern "C" int ms_render_bwd_rows(int64_t N, int CDIM, int W, int H, int tile_si
                                 rows, stream, redo_counts_host);
 }
 
+static int render_bwd_finish_impl(int64_t N, const float *means3d, const float *scales, int scales_are_log, const float *quats,
+                                  const float *opacities, int CDIM, const float *viewmat, float fx, float fy, float cx, float cy,
+                                  int W, int H, float eps2d, const float *rows, float *v_means3d, float *v_scales, float *v_quats,
+                                  float *v_opacities, float *v_colors, float *v_viewmat, void *pose_scratch, void *stream) {
+    MS_REQUIRE(N >= 0 && CDIM == 3 && v_means3d && v_scales && v_quats && v_opacities && v_colors, MS_ERR_INVALID_ARG,
+               "render_bwd_finish: bad argument");
+    if (N == 0) {
+        if (v_viewmat) MS_HIP(hipMemsetAsync(v_viewmat, 0, 16 * sizeof(float), (hipStream_t)stream));
+        return MS_OK;
+    }
+    MS_REQUIRE(rows && opacities, MS_ERR_INVALID_ARG, "render_bwd_finish: null pointer");
+    return ms::project_bwd_from_rows(N, means3d, scales, scales_are_log, quats, viewmat, fx, fy, cx, cy, W, H, eps2d, nullptr, rows, CDIM,
+                                     v_means3d, v_scales, v_quats, v_colors, v_opacities, stream, opacities, v_viewmat, pose_scratch);
+}
+
 extern "C" int ms_render_bwd_finish(int64_t N, const float *means3d, const float *scales, int scales_are_log, const float *quats,
                                     const float *opacities, int CDIM, const float *viewmat, float fx, float fy, float cx, float cy,
                                     int W, int H, float eps2d, const float *rows, float *v_means3d, float *v_scales, float *v_quats,
                                     float *v_opacities, float *v_colors, void *stream) {
-    MS_REQUIRE(N >= 0 && CDIM == 3 && v_means3d && v_scales && v_quats && v_opacities && v_colors, MS_ERR_INVALID_ARG,
-               "render_bwd_finish: bad argument");
-    if (N == 0) return MS_OK;
-    MS_REQUIRE(rows && opacities, MS_ERR_INVALID_ARG, "render_bwd_finish: null pointer");
-    return ms::project_bwd_from_rows(N, means3d, scales, scales_are_log, quats, viewmat, fx, fy, cx, cy, W, H, eps2d, nullptr, rows, CDIM,
-                                     v_means3d, v_scales, v_quats, v_colors, v_opacities, stream, opacities);
+    return render_bwd_finish_impl(N, means3d, scales, scales_are_log, quats, opacities, CDIM, viewmat, fx, fy, cx, cy, W, H, eps2d, rows,
+                                  v_means3d, v_scales, v_quats, v_opacities, v_colors, nullptr, nullptr, stream);
 }
 
-extern "C" int ms_render_bwd(int64_t N, const float *means3d, const float *scales, int scales_are_log, const float *quats,
-                             const float *opacities, const float *colors, int CDIM, const float *viewmat, float fx, float fy,
-                             float cx, float cy, int W, int H, float eps2d, int tile_size, const float *backgrounds,
-                             const void *workspace, size_t workspace_bytes, const void *isect_buf, size_t isect_bytes,
-                             const int64_t *host_info, const float *render_colors, const float *render_alphas,
-                             const int32_t *last_ids, const float *v_render_colors, const float *v_render_alphas,
-                             float *v_means3d, float *v_scales, float *v_quats, float *v_opacities, float *v_colors,
-                             void *bwd_workspace, size_t bwd_workspace_bytes, void *mid_event, void *stream_) {
+extern "C" int ms_render_bwd_finish_pose(int64_t N, const float *means3d, const float *scales, int scales_are_log, const float *quats,
+                                         const float *opacities, int CDIM, const float *viewmat, float fx, float fy, float cx, float cy,
+                                         int W, int H, float eps2d, const float *rows, float *v_means3d, float *v_scales,
+                                         float *v_quats, float *v_opacities, float *v_colors, float *v_viewmat, void *pose_scratch,
+                                         size_t pose_scratch_bytes, void *stream) {
+    if (v_viewmat)
+        if (int rc = ms::check_pose_out(N, v_viewmat, pose_scratch, pose_scratch_bytes, "render_bwd_finish")) return rc;
+    return render_bwd_finish_impl(N, means3d, scales, scales_are_log, quats, opacities, CDIM, viewmat, fx, fy, cx, cy, W, H, eps2d, rows,
+                                  v_means3d, v_scales, v_quats, v_opacities, v_colors, v_viewmat, pose_scratch, stream);
+}
+
+static int render_bwd_impl(int64_t N, const float *means3d, const float *scales, int scales_are_log, const float *quats,
+                           const float *opacities, const float *colors, int CDIM, const float *viewmat, float fx, float fy,
+                           float cx, float cy, int W, int H, float eps2d, int tile_size, const float *backgrounds,
+                           const void *workspace, size_t workspace_bytes, const void *isect_buf, size_t isect_bytes,
+                           const int64_t *host_info, const float *render_colors, const float *render_alphas,
+                           const int32_t *last_ids, const float *v_render_colors, const float *v_render_alphas,
+                           float *v_means3d, float *v_scales, float *v_quats, float *v_opacities, float *v_colors,
+                           void *bwd_workspace, size_t bwd_workspace_bytes, void *mid_event, float *v_viewmat, void *pose_scratch,
+                           size_t pose_scratch_bytes, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     MS_REQUIRE(N >= 0 && W > 0 && H > 0 && tile_size > 0 && CDIM >= 1 && CDIM <= 32, MS_ERR_INVALID_ARG, "render_bwd: bad sizes");
     MS_REQUIRE(host_info && v_means3d && v_scales && v_quats && v_opacities && v_colors, MS_ERR_INVALID_ARG,
                "render_bwd: null pointer");
+    if (v_viewmat)
+        if (int rc = ms::check_pose_out(N, v_viewmat, pose_scratch, pose_scratch_bytes, "render_bwd")) return rc;
+    if (v_viewmat && (N == 0 || host_info[6] == 0 || host_info[0] == 0))   // (an empty frame: constant in the pose too)
+        MS_HIP(hipMemsetAsync(v_viewmat, 0, 16 * sizeof(float), stream));
     if (N == 0) return MS_OK;
     const int64_t M = host_info[0], n_xl = host_info[4];
     if (host_info[6] == 0 || M == 0) {
@@ -827,7 +854,8 @@ extern "C" int ms_render_bwd(int64_t N, const float *means3d, const float *scale
             return rc;
         if (mid_event) MS_HIP(hipEventRecord((hipEvent_t)mid_event, stream));
         return ms::project_bwd_from_rows(N, means3d, scales, scales_are_log, quats, viewmat, fx, fy, cx, cy, W, H, eps2d, nullptr,
-                                         (const float *)bw, CDIM, v_means3d, v_scales, v_quats, v_colors, v_opacities, stream_, opacities);
+                                         (const float *)bw, CDIM, v_means3d, v_scales, v_quats, v_colors, v_opacities, stream_, opacities,
+                                         v_viewmat, pose_scratch);
     }
     MS_REQUIRE(last_ids, MS_ERR_INVALID_ARG, "render_bwd: this frame needs last_ids");
     if (int rc = ms::rasterize_bwd(N, M, means2d, conics, colors, CDIM, opacities, backgrounds, W, H, tile_size, ranges, ids,
@@ -840,9 +868,41 @@ extern "C" int ms_render_bwd(int64_t N, const float *means3d, const float *scale
     if (mid_event) MS_HIP(hipEventRecord((hipEvent_t)mid_event, stream));   // (in-situ timing: between the two stages)
     if (packed_rows)
         return ms::project_bwd_from_rows(N, means3d, scales, scales_are_log, quats, viewmat, fx, fy, cx, cy, W, H, eps2d, radii,
-                                         (const float *)bw, CDIM, v_means3d, v_scales, v_quats, v_colors, v_opacities, stream_);
-    return ms_project_gaussians_bwd(N, means3d, scales, scales_are_log, quats, viewmat, fx, fy, cx, cy, W, H, eps2d, radii,
-                                    v_means2d, v_conics, nullptr, v_means3d, v_scales, v_quats, stream_);
+                                         (const float *)bw, CDIM, v_means3d, v_scales, v_quats, v_colors, v_opacities, stream_, nullptr,
+                                         v_viewmat, pose_scratch);
+    return ms_project_gaussians_bwd_pose(N, means3d, scales, scales_are_log, quats, viewmat, fx, fy, cx, cy, W, H, eps2d, radii,
+                                         v_means2d, v_conics, nullptr, v_means3d, v_scales, v_quats, v_viewmat, pose_scratch,
+                                         pose_scratch_bytes, stream_);
+}
+
+extern "C" int ms_render_bwd(int64_t N, const float *means3d, const float *scales, int scales_are_log, const float *quats,
+                             const float *opacities, const float *colors, int CDIM, const float *viewmat, float fx, float fy,
+                             float cx, float cy, int W, int H, float eps2d, int tile_size, const float *backgrounds,
+                             const void *workspace, size_t workspace_bytes, const void *isect_buf, size_t isect_bytes,
+                             const int64_t *host_info, const float *render_colors, const float *render_alphas,
+                             const int32_t *last_ids, const float *v_render_colors, const float *v_render_alphas,
+                             float *v_means3d, float *v_scales, float *v_quats, float *v_opacities, float *v_colors,
+                             void *bwd_workspace, size_t bwd_workspace_bytes, void *mid_event, void *stream) {
+    return render_bwd_impl(N, means3d, scales, scales_are_log, quats, opacities, colors, CDIM, viewmat, fx, fy, cx, cy, W, H, eps2d,
+                           tile_size, backgrounds, workspace, workspace_bytes, isect_buf, isect_bytes, host_info, render_colors,
+                           render_alphas, last_ids, v_render_colors, v_render_alphas, v_means3d, v_scales, v_quats, v_opacities,
+                           v_colors, bwd_workspace, bwd_workspace_bytes, mid_event, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int ms_render_bwd_pose(int64_t N, const float *means3d, const float *scales, int scales_are_log, const float *quats,
+                                  const float *opacities, const float *colors, int CDIM, const float *viewmat, float fx, float fy,
+                                  float cx, float cy, int W, int H, float eps2d, int tile_size, const float *backgrounds,
+                                  const void *workspace, size_t workspace_bytes, const void *isect_buf, size_t isect_bytes,
+                                  const int64_t *host_info, const float *render_colors, const float *render_alphas,
+                                  const int32_t *last_ids, const float *v_render_colors, const float *v_render_alphas,
+                                  float *v_means3d, float *v_scales, float *v_quats, float *v_opacities, float *v_colors,
+                                  void *bwd_workspace, size_t bwd_workspace_bytes, void *mid_event, float *v_viewmat,
+                                  void *pose_scratch, size_t pose_scratch_bytes, void *stream) {
+    return render_bwd_impl(N, means3d, scales, scales_are_log, quats, opacities, colors, CDIM, viewmat, fx, fy, cx, cy, W, H, eps2d,
+                           tile_size, backgrounds, workspace, workspace_bytes, isect_buf, isect_bytes, host_info, render_colors,
+                           render_alphas, last_ids, v_render_colors, v_render_alphas, v_means3d, v_scales, v_quats, v_opacities,
+                           v_colors, bwd_workspace, bwd_workspace_bytes, mid_event, v_viewmat, pose_scratch, pose_scratch_bytes,
+                           stream);
 }
 
 

@@ -14,6 +14,7 @@
 // The basis is evaluated once, in a scalar type T: float for values, a 3-direction dual number
 // for the derivatives the backward needs (no hand-derived gradient tables to get wrong).
 #include "ms_common.hpp"
+#include "pose_grad.hpp"
 
 namespace {
 
@@ -181,20 +182,25 @@ __global__ __launch_bounds__(kShThreads) void k_sh_fwd(ShArgs A, const float *__
 
 // Backward.  v_coeffs[g,k,c] = b_k * v_c (zero rows beyond the used degree and for masked
 // Gaussians); v_means3d = J_normalise^T * sum_k sum_c coeff[k,c] v_c grad(b_k).
-template <int DEG>
+// POSE: the camera centre's gradient too -- minus the sum of those v_means3d (the direction is mean - camera) -- summed over
+// the workgroup into row blockIdx.x of campos_slab (pose_grad.hpp); every wave then runs to the block sum (a wave wholly
+// past N with zero terms), and the directional gradient is formed even where v_means3d is null.
+template <int DEG, bool POSE = false>
 __global__ __launch_bounds__(kShThreads) void k_sh_bwd(ShArgs A, const float *__restrict__ means3d,
                                                        const float *__restrict__ coeffs,
                                                        const int32_t *__restrict__ radii,
                                                        const float *__restrict__ colors_fwd,
                                                        const float *__restrict__ v_colors,
-                                                       float *__restrict__ v_coeffs, float *__restrict__ v_means3d) {
+                                                       float *__restrict__ v_coeffs, float *__restrict__ v_means3d,
+                                                       float *__restrict__ campos_slab) {
     constexpr int KU = (DEG + 1) * (DEG + 1);
     constexpr int STR = ShCfg<KU>::STR;
     extern __shared__ float s_all[];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     float *s_rec = s_all + (size_t)w * 64 * STR;
     const int64_t g0 = ((int64_t)blockIdx.x * (kShThreads / 64) + w) * 64;
-    if (g0 >= A.N) return;
+    if constexpr (!POSE)
+        if (g0 >= A.N) return;
     const int64_t g = g0 + lane;
     bool on = g < A.N;
     if (on && radii) {
@@ -202,7 +208,8 @@ __global__ __launch_bounds__(kShThreads) void k_sh_bwd(ShArgs A, const float *__
         on = r.x > 0 && r.y > 0;
     }
     const unsigned long long active = __ballot(on);
-    if (v_means3d) {
+    float cp[3] = {0.f, 0.f, 0.f};   // POSE: this Gaussian's term of dL/dcampos
+    if (POSE || v_means3d) {
         stage_records<KU>(coeffs, g0, A.N, A.K, active, s_rec);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -222,7 +229,7 @@ __global__ __launch_bounds__(kShThreads) void k_sh_bwd(ShArgs A, const float *__
         float x = means3d[3 * g] - A.cx, y = means3d[3 * g + 1] - A.cy, z = means3d[3 * g + 2] - A.cz;
         const float inorm = rsqrtf(x * x + y * y + z * z);
         x *= inorm; y *= inorm; z *= inorm;
-        if (v_means3d) {
+        if (POSE || v_means3d) {
             Dual3 b[KU];
             sh_basis<DEG, Dual3>(Dual3{x, 1.f, 0.f, 0.f}, Dual3{y, 0.f, 1.f, 0.f}, Dual3{z, 0.f, 0.f, 1.f}, b);
             const float *rec = s_rec + lane * STR;
@@ -235,14 +242,21 @@ __global__ __launch_bounds__(kShThreads) void k_sh_bwd(ShArgs A, const float *__
             }
             // through d = p / |p|: (I - d d^T) u / |p|
             const float dot = ux * x + uy * y + uz * z;
-            v_means3d[3 * g] = (ux - dot * x) * inorm;
-            v_means3d[3 * g + 1] = (uy - dot * y) * inorm;
-            v_means3d[3 * g + 2] = (uz - dot * z) * inorm;
+            if (!POSE || v_means3d) {
+                v_means3d[3 * g] = (ux - dot * x) * inorm;
+                v_means3d[3 * g + 1] = (uy - dot * y) * inorm;
+                v_means3d[3 * g + 2] = (uz - dot * z) * inorm;
+            }
+            if constexpr (POSE) { cp[0] = -((ux - dot * x) * inorm); cp[1] = -((uy - dot * y) * inorm); cp[2] = -((uz - dot * z) * inorm); }
         } else {
             sh_basis<DEG, float>(x, y, z, bval);
         }
     } else if (g < A.N && v_means3d) {
         v_means3d[3 * g] = 0.f; v_means3d[3 * g + 1] = 0.f; v_means3d[3 * g + 2] = 0.f;
+    }
+    if constexpr (POSE) {
+        ms::pose_block_sum_store<3>(cp, campos_slab + (int64_t)blockIdx.x * ms::kPoseSlabStride);
+        if (g0 >= A.N) return;   // (past N: no rows of v_coeffs)
     }
     if (!v_coeffs) return;
     // outer products through LDS so the K*12-byte rows leave as coalesced stores
@@ -307,17 +321,27 @@ int launch_fwd(const ShArgs &A, const float *means3d, const float *coeffs, const
 template <int DEG>
 int launch_bwd(const ShArgs &A, const float *means3d, const float *coeffs, const int32_t *radii,
                const float *colors_fwd, const float *v_colors, float *v_coeffs, float *v_means3d,
-               hipStream_t stream) {
+               hipStream_t stream, float *v_campos, void *pose_scratch) {
     constexpr int KU = (DEG + 1) * (DEG + 1);
     const unsigned grid = (unsigned)ms::ceil_div(A.N, kShThreads);
     const size_t lds = ShCfg<KU>::LDS;
+    if (!v_campos) {
+        if (lds > 48 * 1024)
+            MS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sh_bwd<DEG>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((k_sh_bwd<DEG>), dim3(grid), dim3(kShThreads), lds, stream, A, means3d, coeffs, radii,
+                           colors_fwd, v_colors, v_coeffs, v_means3d, (float *)nullptr);
+        MS_LAUNCH_CHECK();
+        return MS_OK;
+    }
     if (lds > 48 * 1024)
-        MS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sh_bwd<DEG>),
+        MS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sh_bwd<DEG, true>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_sh_bwd<DEG>), dim3(grid), dim3(kShThreads), lds, stream, A, means3d, coeffs, radii,
-                       colors_fwd, v_colors, v_coeffs, v_means3d);
+    float *slab = (float *)pose_scratch;
+    hipLaunchKernelGGL((k_sh_bwd<DEG, true>), dim3(grid), dim3(kShThreads), lds, stream, A, means3d, coeffs, radii,
+                       colors_fwd, v_colors, v_coeffs, v_means3d, slab);
     MS_LAUNCH_CHECK();
-    return MS_OK;
+    return ms::pose_slab_sum(slab, grid, 3, v_campos, 3, stream);
 }
 
 int check_sh(int64_t N, int K, int degree, const char *what) {
@@ -352,24 +376,44 @@ extern "C" int ms_spherical_harmonics_fwd(int64_t N, int K, int degree, const fl
     }
 }
 
-extern "C" int ms_spherical_harmonics_bwd(int64_t N, int K, int degree, const float *means3d, float cam_x,
-                                          float cam_y, float cam_z, const float *coeffs, const int32_t *radii,
-                                          int add_half_and_clamp, const float *colors_fwd, const float *v_colors,
-                                          float *v_coeffs, float *v_means3d, void *stream_) {
+static int sh_bwd_impl(int64_t N, int K, int degree, const float *means3d, float cam_x, float cam_y, float cam_z,
+                       const float *coeffs, const int32_t *radii, int add_half_and_clamp, const float *colors_fwd,
+                       const float *v_colors, float *v_coeffs, float *v_means3d, float *v_campos, void *pose_scratch,
+                       void *stream_) {
     if (int rc = check_sh(N, K, degree, "sh_bwd")) return rc;
-    if (N == 0) return MS_OK;
-    MS_REQUIRE(means3d && v_colors && (v_coeffs || v_means3d), MS_ERR_INVALID_ARG, "sh_bwd: null pointer");
-    MS_REQUIRE(!v_means3d || coeffs, MS_ERR_INVALID_ARG, "sh_bwd: v_means3d needs the coefficients");
+    if (N == 0) return v_campos ? ms::pose_slab_sum(nullptr, 0, 3, v_campos, 3, stream_) : MS_OK;
+    MS_REQUIRE(means3d && v_colors && (v_coeffs || v_means3d || v_campos), MS_ERR_INVALID_ARG, "sh_bwd: null pointer");
+    MS_REQUIRE(!(v_means3d || v_campos) || coeffs, MS_ERR_INVALID_ARG, "sh_bwd: v_means3d / v_campos need the coefficients");
     MS_REQUIRE(!add_half_and_clamp || colors_fwd, MS_ERR_INVALID_ARG,
                "sh_bwd: the clamped form needs the forward colours (f32)");
     MS_REQUIRE(((uintptr_t)radii & 7) == 0, MS_ERR_INVALID_ARG, "sh_bwd: radii must be 8-byte aligned");
     const ShArgs A{N, K, cam_x, cam_y, cam_z, add_half_and_clamp};
     hipStream_t stream = (hipStream_t)stream_;
+    void *ps = pose_scratch;
     switch (degree) {
-        case 0: return launch_bwd<0>(A, means3d, coeffs, radii, colors_fwd, v_colors, v_coeffs, v_means3d, stream);
-        case 1: return launch_bwd<1>(A, means3d, coeffs, radii, colors_fwd, v_colors, v_coeffs, v_means3d, stream);
-        case 2: return launch_bwd<2>(A, means3d, coeffs, radii, colors_fwd, v_colors, v_coeffs, v_means3d, stream);
-        case 3: return launch_bwd<3>(A, means3d, coeffs, radii, colors_fwd, v_colors, v_coeffs, v_means3d, stream);
-        default: return launch_bwd<4>(A, means3d, coeffs, radii, colors_fwd, v_colors, v_coeffs, v_means3d, stream);
+        case 0: return launch_bwd<0>(A, means3d, coeffs, radii, colors_fwd, v_colors, v_coeffs, v_means3d, stream, v_campos, ps);
+        case 1: return launch_bwd<1>(A, means3d, coeffs, radii, colors_fwd, v_colors, v_coeffs, v_means3d, stream, v_campos, ps);
+        case 2: return launch_bwd<2>(A, means3d, coeffs, radii, colors_fwd, v_colors, v_coeffs, v_means3d, stream, v_campos, ps);
+        case 3: return launch_bwd<3>(A, means3d, coeffs, radii, colors_fwd, v_colors, v_coeffs, v_means3d, stream, v_campos, ps);
+        default: return launch_bwd<4>(A, means3d, coeffs, radii, colors_fwd, v_colors, v_coeffs, v_means3d, stream, v_campos, ps);
     }
+}
+
+extern "C" int ms_spherical_harmonics_bwd(int64_t N, int K, int degree, const float *means3d, float cam_x,
+                                          float cam_y, float cam_z, const float *coeffs, const int32_t *radii,
+                                          int add_half_and_clamp, const float *colors_fwd, const float *v_colors,
+                                          float *v_coeffs, float *v_means3d, void *stream) {
+    return sh_bwd_impl(N, K, degree, means3d, cam_x, cam_y, cam_z, coeffs, radii, add_half_and_clamp, colors_fwd, v_colors,
+                       v_coeffs, v_means3d, nullptr, nullptr, stream);
+}
+
+extern "C" int ms_spherical_harmonics_bwd_pose(int64_t N, int K, int degree, const float *means3d, float cam_x, float cam_y,
+                                               float cam_z, const float *coeffs, const int32_t *radii, int add_half_and_clamp,
+                                               const float *colors_fwd, const float *v_colors, float *v_coeffs,
+                                               float *v_means3d, float *v_campos, void *pose_scratch, size_t pose_scratch_bytes,
+                                               void *stream) {
+    if (v_campos)
+        if (int rc = ms::check_pose_out(N, v_campos, pose_scratch, pose_scratch_bytes, "sh_bwd")) return rc;
+    return sh_bwd_impl(N, K, degree, means3d, cam_x, cam_y, cam_z, coeffs, radii, add_half_and_clamp, colors_fwd, v_colors,
+                       v_coeffs, v_means3d, v_campos, pose_scratch, stream);
 }

@@ -711,7 +711,12 @@ def render_gaussians_trainable_sharded(means3d, scales, quats, opacities, featur
         raster(means2d, conics, colors, opacities, bg, ranges, ids, camera, tile_size) -> (H, W, C) image
     rehearse=(rank, world) (HIP path): that rank's share of the step WITHOUT a process group and without the two exchanges --
     its band's forward and backward, gradients of its band's pixels only: single-GPU timing of one rank (scripts/band_train_bench.py).
-    The reference has no counterpart (no backward: render.py:11; no distributed path)."""
+    The reference has no counterpart (no backward: render.py:11; no distributed path).
+    A camera whose view_matrix requires grad is refused (ValueError): the pose gradient would need an all-reduce of its own
+    over the ranks, which this path does not do -- render_gaussians_trainable differentiates the pose on one GPU."""
+    if camera.view_matrix is not None and camera.view_matrix.requires_grad:
+        raise ValueError("render_gaussians_trainable_sharded: no gradient w.r.t. the camera pose (view_matrix requires grad); "
+                         "use render_gaussians_trainable")
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     if rehearse is not None:

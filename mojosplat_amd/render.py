@@ -273,12 +273,14 @@ def render_gaussians(
     frame -- autograd.render_gaussians_trainable: one forward library call that keeps its alphas, the quad-wave backward --
     and every other call is the inference frame below, run under no_grad exactly as the reference runs.  (bin_size and
     async_op are inference-frame arguments; a differentiable call ignores bin_size -- the pixels and the gradients do not
-    depend on the binning grid -- and refuses async_op.)"""
+    depend on the binning grid -- and refuses async_op.)  A camera.view_matrix that requires grad makes the call
+    differentiable too: its .grad is the gradient w.r.t. the camera pose."""
     # (round 6, advisor: the differentiable frame is for CUDA tensors only -- CPU inputs fall through to the reference's
     # "must be CUDA tensors" ValueError below instead of failing inside the autograd wrapper)
     if backend == "hip" and torch.is_grad_enabled() and all(
             isinstance(t, torch.Tensor) and t.is_cuda for t in (means3d, scales, quats, opacities, features)) and any(
-            isinstance(t, torch.Tensor) and t.requires_grad for t in (means3d, scales, quats, opacities, features, background_color)):
+            isinstance(t, torch.Tensor) and t.requires_grad
+            for t in (means3d, scales, quats, opacities, features, background_color, camera.view_matrix)):
         if async_op:
             raise ValueError("async_op: a differentiable frame is rendered by the blocking call")
         from .autograd import render_gaussians_trainable

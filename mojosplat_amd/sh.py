@@ -10,7 +10,7 @@ direction = normalise(mean - camera position), colour = max(sum_k b_k(dir) * coe
     image  = render_gaussians(means3d, scales, quats, opac, sh_coeffs, cam, sh_degree=3)
 
 `sh_coeffs` is (N, K, 3) with K >= (sh_degree+1)^2.  backend="hip" runs csrc/sh.hip (forward and
-backward, differentiable w.r.t. the coefficients and the means); backend="torch" is a plain
+backward, differentiable w.r.t. the coefficients, the means and -- through the camera centre -- camera.view_matrix); backend="torch" is a plain
 PyTorch restatement for CPU tensors.  2-D features keep the reference's placeholder behaviour.
 """
 from typing import Optional
@@ -78,8 +78,11 @@ def evaluate_sh_torch(means3d, sh_coeffs, camera: Camera, sh_degree: int, radii=
 
 
 class _ShHip(torch.autograd.Function):
+    # campos: the camera centre as host floats (what the kernels read); campos_t: the same centre as a differentiable
+    # tensor (camera_position), or None -- its gradient (dL/dcampos, ms_spherical_harmonics_bwd_pose) is the SH colours'
+    # share of the camera-pose gradient
     @staticmethod
-    def forward(ctx, means3d, sh_coeffs, campos, sh_degree, radii, clamp, half):
+    def forward(ctx, means3d, sh_coeffs, campos, sh_degree, radii, clamp, half, campos_t=None):
         L = _hip.lib()
         means3d, sh_coeffs = _hip.f32c(means3d), _hip.f32c(sh_coeffs)
         N, K = sh_coeffs.shape[0], sh_coeffs.shape[1]
@@ -93,6 +96,7 @@ class _ShHip(torch.autograd.Function):
                 _hip.ptr(radii), int(clamp), 1 if half else 0, _hip.ptr(colors), _hip.stream(dev)),
                 "ms_spherical_harmonics_fwd")
         ctx.cfg = (campos, sh_degree, clamp, half)
+        ctx.cp_meta = None if campos_t is None else (campos_t.dtype, campos_t.device)
         ctx.save_for_backward(means3d, sh_coeffs, radii, colors)
         return colors
 
@@ -104,23 +108,37 @@ class _ShHip(torch.autograd.Function):
         N, K = sh_coeffs.shape[0], sh_coeffs.shape[1]
         dev = means3d.device
         need_c, need_m = ctx.needs_input_grad[1], ctx.needs_input_grad[0]
+        need_p = ctx.cp_meta is not None and ctx.needs_input_grad[7]
         v_coeffs = torch.empty_like(sh_coeffs) if need_c else None
         v_means = torch.empty_like(means3d) if need_m else None
-        if need_c or need_m:
+        v_campos = None
+        if need_p:
+            v_campos = torch.empty(3, dtype=torch.float32, device=dev)
+            pws = torch.empty(L.ms_pose_scratch_bytes(N), dtype=torch.uint8, device=dev)
+            with _hip.on_device(dev):
+                _hip.check(L.ms_spherical_harmonics_bwd_pose(
+                    N, K, sh_degree, _hip.ptr(means3d), campos[0], campos[1], campos[2], _hip.ptr(sh_coeffs),
+                    _hip.ptr(radii), int(clamp), _hip.ptr(colors.float() if half else colors),
+                    _hip.ptr(_hip.f32c(v_colors)), _hip.ptr(v_coeffs), _hip.ptr(v_means), _hip.ptr(v_campos), _hip.ptr(pws),
+                    pws.numel(), _hip.stream(dev)), "ms_spherical_harmonics_bwd_pose")
+            v_campos = v_campos.to(device=ctx.cp_meta[1], dtype=ctx.cp_meta[0])
+        elif need_c or need_m:
             with _hip.on_device(dev):
                 _hip.check(L.ms_spherical_harmonics_bwd(
                     N, K, sh_degree, _hip.ptr(means3d), campos[0], campos[1], campos[2], _hip.ptr(sh_coeffs),
                     _hip.ptr(radii), int(clamp), _hip.ptr(colors.float() if half else colors),
                     _hip.ptr(_hip.f32c(v_colors)), _hip.ptr(v_coeffs), _hip.ptr(v_means), _hip.stream(dev)),
                     "ms_spherical_harmonics_bwd")
-        return v_means, v_coeffs, None, None, None, None, None
+        return v_means, v_coeffs, None, None, None, None, None, v_campos
 
 
 def evaluate_sh_hip(means3d, sh_coeffs, camera: Camera, sh_degree: int, radii=None, clamp=True, half=False):
     _check(means3d, sh_coeffs, sh_degree)
     _hip.require_cuda(means3d, sh_coeffs, radii)
     campos = camera._campos()
-    return _ShHip.apply(means3d, sh_coeffs, campos, int(sh_degree), radii, bool(clamp), bool(half))
+    # a view matrix that requires grad: the camera centre -R^T t enters as a tensor too (the kernels keep their floats)
+    campos_t = camera_position(camera) if camera.view_matrix.requires_grad and torch.is_grad_enabled() else None
+    return _ShHip.apply(means3d, sh_coeffs, campos, int(sh_degree), radii, bool(clamp), bool(half), campos_t)
 
 
 def evaluate_sh(means3d: torch.Tensor, sh_coeffs: torch.Tensor, camera: Camera, sh_degree: int,

@@ -1,0 +1,449 @@
+"""GPU: gradients w.r.t. the camera pose (camera.view_matrix) on every differentiable route.
+
+The pose gradient is summed over the Gaussians without atomics: k_project_ewa_bwd<ROWS, STATS, POSE = true> leaves one
+partial per workgroup, k_pose_slab_sum adds them in a fixed order (csrc/pose_grad.hpp); the SH colours' share reaches the
+view matrix through the camera centre -R^T t (k_sh_bwd<DEG, true>).
+
+  1. against float64 autograd of torch_oracle.project (+ sh_colors) + rasterize on the HIP forward's own lists, with the
+     branch guard of test_hip_backward_paths.py (Upstream), on every route: the lean fused frame on 16 / 32 / 64-px bins,
+     the non-lean fused frame (C = 1, 4; tile sizes 8, 24), stagewise=True, project_gaussians_autograd, SH degrees 0-3;
+     on a square centred camera and a non-square, off-centre one (clamped Jacobians, culled Gaussians);
+  2. nothing else moves: on the same upstream gradients, every Gaussian gradient and the DensifyStats buffers are
+     bit-identical with the pose on or off (through the C ABI; end to end on every route to the rasterisers' rounding);
+  3. deterministic: the same upstream gradients give the same v_viewmat bits; a retain_graph second backward; an empty
+     frame gives zeros;
+  4. the public surface: .grad reaches leaf R / T of a Camera and `eye` of look_at;
+  5. pose recovery with Adam on an se(3) parameter;
+  6. the sharded trainer refuses a pose that requires grad.
+"""
+import numpy as np
+import pytest
+import torch
+
+from helpers import assert_grad_close, general_camera, general_scene, np_
+from mojosplat_amd import Camera, _hip, render_gaussians
+from mojosplat_amd.autograd import project_gaussians_autograd, render_gaussians_trainable
+from mojosplat_amd.binning import bin_gaussians_to_tiles_hip
+from mojosplat_amd.densify import DensifyStats
+from mojosplat_amd.projection import EPS2D
+from mojosplat_amd.scenes import randscene_v1
+from mojosplat_amd.sh import evaluate_sh_hip
+from mojosplat_amd.utils import look_at
+from oracle import torch_oracle
+from test_hip_backward_paths import Upstream, _background
+
+pytestmark = pytest.mark.gpu
+
+NAMES = ("means3d", "scales", "quats", "opacities", "features")
+
+
+def _posed(cam, requires_grad=True):
+    """The same camera with its view matrix a leaf of its own."""
+    vm = cam.view_matrix.detach().clone().requires_grad_(requires_grad)
+    return Camera(R=cam.R, T=cam.T, H=cam.H, W=cam.W, fx=cam.fx, fy=cam.fy, cx=cam.cx, cy=cam.cy, near=cam.near,
+                  far=cam.far, view_matrix=vm)
+
+
+def _square_scene(device, C=3, seed=0, sh=None):
+    sc, cam = randscene_v1(300, 96, 96, ell=-2.5, seed=seed, device=device, channels=C)
+    if sh is not None:
+        K = (sh + 1) ** 2
+        g = torch.Generator().manual_seed(seed + 7)
+        sc["features"] = (torch.randn(300, K, 3, generator=g) * 0.3).to(device)
+    return sc, cam
+
+
+def _general_scene(device, C=3, seed=0, sh=None):
+    cam = general_camera(330, 190, 300.0, 240.0, 0.35 * 330, 0.62 * 190, device=device)
+    sc, _ = general_scene(cam, n_view=500, n_side=16, n_plane=12, n_cull=12, seed=seed, channels=C)
+    if sh is not None:
+        g = torch.Generator().manual_seed(seed + 7)
+        sc["features"] = torch.randn(sc["means3d"].shape[0], (sh + 1) ** 2, 3, generator=g) * 0.3
+    return {k: v.to(device) for k, v in sc.items()}, cam
+
+
+def _pose_vs_f64(device, sc, cam, ts, seed, *, stagewise=False, sh=None, monkeypatch=None, bin_px=None, tag=""):
+    C = 3 if sh is not None else sc["features"].shape[-1]
+    leaves = [sc[k].clone().requires_grad_(True) for k in NAMES]
+    bg = _background(C, seed, device)
+    H, W = cam.H, cam.W
+    th, tw = -(-H // ts), -(-W // ts)
+    with torch.no_grad():
+        m2h, conh, deph, radh = project_gaussians_autograd(*[l.detach() for l in leaves[:4]], cam)
+        ids, ranges = bin_gaussians_to_tiles_hip(m2h, radh, deph, ts, tw, th)
+        cols = evaluate_sh_hip(leaves[0].detach(), leaves[4].detach(), cam, sh) if sh is not None else leaves[4].detach()
+    ids_c, ranges_c = np_(ids).astype(np.int32), np_(ranges).astype(np.int32)
+    up = Upstream(np_(m2h), np_(conh), np_(cols.float()), np_(leaves[3]), bg, ranges_c, ids_c, H, W, ts, seed=seed + 1)
+    pcam = _posed(cam)
+    if bin_px is not None:
+        monkeypatch.setenv("MOJOSPLAT_TRAIN_BIN_PX", str(bin_px))
+    img = render_gaussians_trainable(*leaves, pcam, background_color=bg, tile_size=ts, sh_degree=sh, stagewise=stagewise)
+    img.backward(up.v_img.to(device))
+    assert pcam.view_matrix.grad is not None, f"{tag}: no pose gradient"
+    # float64 reference
+    rl = [l.detach().cpu().double() for l in leaves]
+    vm64 = cam.view_matrix.detach().cpu().double().requires_grad_(True)
+    rm2, rcon, _ = torch_oracle.project(rl[0], rl[1], rl[2], vm64, cam.fx, cam.fy, cam.cx, cam.cy, W, H)
+    if sh is not None:
+        campos = -(vm64[:3, :3].T @ vm64[:3, 3])
+        rcol = torch_oracle.sh_colors(rl[0], campos, rl[4], sh)
+    else:
+        rcol = rl[4]
+    rimg, _ = torch_oracle.rasterize(rm2, rcon, rcol, rl[3], bg.double().cpu(), torch.from_numpy(ranges_c),
+                                     torch.from_numpy(ids_c), H, W, ts)
+    keep = ~up.guard
+    # (the image as test_hip_backward_paths.py checks it, on the centred camera; the general scenes' near-plane Gaussians
+    # move single pixels by up to ~2e-3 in fp32 -- the forward is not what this file tests)
+    err = np.abs(np_(img) - rimg.detach().numpy())[keep]
+    assert err.max() <= (2e-4 if cam.cx == 0.5 * W else 5e-3) and np.quantile(err, 0.999) <= 2e-4, f"{tag}: image"
+    (rimg * up.v_img.double()).sum().backward()
+    g = pcam.view_matrix.grad
+    assert g.dtype == pcam.view_matrix.dtype and g.device == pcam.view_matrix.device
+    assert torch.all(g[3] == 0), f"{tag}: bottom row"
+    assert_grad_close(f"{tag}/viewmat", g, vm64.grad, rel=2e-3)
+    return g
+
+
+SCENES = {"square": _square_scene, "general": _general_scene}
+
+
+# ------------------------------------------------------------------ 1. against float64
+@pytest.mark.parametrize("scene", ["square", "general"])
+@pytest.mark.parametrize("bin_px", [16, 32, 64])
+def test_lean_frame_pose_vs_f64(device, monkeypatch, scene, bin_px):
+    """The lean fused frame (k_project_ewa_bwd<2, false, true>) on 16 / 32 / 64-px bins."""
+    sc, cam = SCENES[scene](device, seed=3)
+    _pose_vs_f64(device, sc, cam, 16, 11, monkeypatch=monkeypatch, bin_px=bin_px, tag=f"lean/{scene}/bin{bin_px}")
+
+
+@pytest.mark.parametrize("scene", ["square", "general"])
+@pytest.mark.parametrize("C,ts", [(1, 16), (4, 16), (3, 8), (3, 24)])
+def test_nonlean_frame_pose_vs_f64(device, scene, C, ts):
+    """ms_render_bwd_pose: the packed rows finished by k_project_ewa_bwd<1, false, true>."""
+    sc, cam = SCENES[scene](device, C=C, seed=5)
+    _pose_vs_f64(device, sc, cam, ts, 13 + C + ts, tag=f"nonlean/{scene}/C{C}/ts{ts}")
+
+
+@pytest.mark.parametrize("scene", ["square", "general"])
+def test_stagewise_pose_vs_f64(device, scene):
+    """stagewise=True: _ProjectHip's ms_project_gaussians_bwd_pose (k_project_ewa_bwd<0, false, true>)."""
+    sc, cam = SCENES[scene](device, seed=6)
+    _pose_vs_f64(device, sc, cam, 16, 17, stagewise=True, tag=f"stagewise/{scene}")
+
+
+@pytest.mark.parametrize("scene", ["square", "general"])
+@pytest.mark.parametrize("degree", [0, 1, 2, 3])
+def test_sh_pose_vs_f64(device, scene, degree):
+    """SH colours: the projection's share plus k_sh_bwd<DEG, true>'s camera-centre gradient chained through -R^T t."""
+    sc, cam = SCENES[scene](device, seed=8 + degree, sh=degree)
+    _pose_vs_f64(device, sc, cam, 16, 19 + degree, sh=degree, tag=f"sh{degree}/{scene}")
+
+
+@pytest.mark.parametrize("scene", ["square", "general"])
+def test_projection_autograd_pose_vs_f64(device, scene):
+    """project_gaussians_autograd with a loss on depths, means2d and conics (culled Gaussians carry no loss)."""
+    sc, cam = SCENES[scene](device, seed=9)
+    leaves = [sc[k].clone().requires_grad_(True) for k in NAMES[:4]]
+    pcam = _posed(cam)
+    m2, con, dep, rad = project_gaussians_autograd(*leaves, pcam)
+    alive = ((rad[:, 0] > 0) & (rad[:, 1] > 0)).cpu()
+    assert 0 < int(alive.sum()) < len(alive) or scene == "square"
+    g = torch.Generator().manual_seed(4)
+    N = len(alive)
+    w2, wc, wd = torch.randn(N, 2, generator=g), torch.randn(N, 3, generator=g), torch.randn(N, generator=g)
+    w2, wc, wd = w2 * alive[:, None], wc * alive[:, None], wd * alive
+    ((m2 * w2.to(device)).sum() + (con * wc.to(device)).sum() + (dep * wd.to(device)).sum()).backward()
+    rl = [l.detach().cpu().double() for l in leaves]
+    vm64 = cam.view_matrix.detach().cpu().double().requires_grad_(True)
+    rm2, rcon, rdep = torch_oracle.project(rl[0], rl[1], rl[2], vm64, cam.fx, cam.fy, cam.cx, cam.cy, cam.W, cam.H)
+    ((rm2 * w2.double()).sum() + (rcon * wc.double()).sum() + (rdep * wd.double()).sum()).backward()
+    assert_grad_close(f"project/{scene}/viewmat", pcam.view_matrix.grad, vm64.grad, rel=2e-3)
+
+
+# ------------------------------------------------------------------ 2. / 3. the kernels on fixed upstream gradients
+# (end to end, the rows and v_means2d the backward rasterisers leave are float-atomic sums whose last bits follow the arrival
+# order: the pose's own sum is pinned here, on the same upstream gradients, through the C ABI)
+def _abi_inputs(device, N=3000, seed=50):
+    sc, cam = randscene_v1(N, 96, 96, ell=-2.5, seed=seed, device=device)
+    g = torch.Generator().manual_seed(seed)
+    rows = torch.rand(N, 16, generator=g) * 2.0 - 1.0
+    rows[torch.rand(N, generator=g) < 0.2] = 0.0                # never blended
+    sc["rows"] = rows.to(device).contiguous()
+    return sc, cam
+
+
+def _p(t):
+    return _hip.ptr(t)
+
+
+def _finish(L, sc, cam, pose, densify=None):
+    N = sc["means3d"].shape[0]
+    dev = sc["means3d"].device
+    out = [torch.empty(N, 3, device=dev), torch.empty(N, 3, device=dev), torch.empty(N, 4, device=dev),
+           torch.empty(N, device=dev), torch.empty(N, 3, device=dev)]
+    vm = cam._viewmat_f32()
+    args = [N, _p(sc["means3d"]), _p(sc["scales"]), 1, _p(sc["quats"]), _p(sc["opacities"]), 3, _p(vm), cam.fx, cam.fy, cam.cx,
+            cam.cy, cam.W, cam.H, EPS2D, _p(sc["rows"])] + [_p(t) for t in out]
+    if densify is not None:
+        args += [cam.near, cam.far] + [_p(t) for t in densify]
+    v_vm = None
+    if pose:
+        v_vm = torch.full((16,), float("nan"), device=dev)
+        pws = torch.full((L.ms_pose_scratch_bytes(N),), 0xFF, dtype=torch.uint8, device=dev)
+        args += [_p(v_vm), _p(pws), pws.numel()]
+    fn = {(False, False): L.ms_render_bwd_finish, (False, True): L.ms_render_bwd_finish_pose,
+          (True, False): L.ms_render_bwd_finish_densify, (True, True): L.ms_render_bwd_finish_densify_pose}[(densify is not None, pose)]
+    _hip.check(fn(*args, _hip.stream(dev)))
+    torch.cuda.synchronize()
+    return out, v_vm
+
+
+@pytest.mark.parametrize("densify", [False, True])
+def test_finish_pose_bit_identical_and_deterministic(device, densify):
+    """k_project_ewa_bwd<2, STATS, true>: the Gaussians' gradients and the statistics exactly those of the pose-free
+    call; v_viewmat the same bits twice (N = 3000: twelve workgroups, the last one partial)."""
+    L = _hip.lib()
+    sc, cam = _abi_inputs(device)
+    N = sc["means3d"].shape[0]
+    st0 = [torch.rand(N, generator=torch.Generator().manual_seed(k)).to(device) for k in range(3)] if densify else None
+    st1 = [t.clone() for t in st0] if densify else None
+    st2 = [t.clone() for t in st0] if densify else None
+    a, _ = _finish(L, sc, cam, False, st0)
+    b, v1 = _finish(L, sc, cam, True, st1)
+    c, v2 = _finish(L, sc, cam, True, st2)
+    for name, x, y in zip(("means3d", "scales", "quats", "opacities", "colors"), a, b):
+        assert torch.equal(x, y), f"{name} moved with the pose on"
+    if densify:
+        for x, y in zip(st0, st1):
+            assert torch.equal(x, y)
+    assert torch.isfinite(v1).all() and torch.all(v1[12:] == 0) and v1.abs().sum() > 0
+    assert torch.equal(v1, v2)
+
+
+def test_projection_bwd_pose_bit_identical_and_deterministic(device):
+    """k_project_ewa_bwd<0, false, true> (ms_project_gaussians_bwd_pose) on fixed v_means2d / v_conics / v_depths."""
+    L = _hip.lib()
+    sc, cam = _abi_inputs(device)
+    N = sc["means3d"].shape[0]
+    with torch.no_grad():
+        _, _, _, radii = project_gaussians_autograd(sc["means3d"], sc["scales"], sc["quats"], sc["opacities"], cam)
+    radii = radii.to(torch.int32).contiguous()
+    g = torch.Generator().manual_seed(5)
+    v2, vc, vd = (torch.randn(N, k, generator=g).squeeze(-1).to(device).contiguous() for k in (2, 3, 1))
+    vm = cam._viewmat_f32()
+
+    def run(pose):
+        out = [torch.empty(N, 3, device=device), torch.empty(N, 3, device=device), torch.empty(N, 4, device=device)]
+        args = [N, _p(sc["means3d"]), _p(sc["scales"]), 1, _p(sc["quats"]), _p(vm), cam.fx, cam.fy, cam.cx, cam.cy, cam.W, cam.H,
+                EPS2D, _p(radii), _p(v2), _p(vc), _p(vd)] + [_p(t) for t in out]
+        if not pose:
+            _hip.check(L.ms_project_gaussians_bwd(*args, _hip.stream(device)))
+            torch.cuda.synchronize()
+            return out, None
+        v_vm = torch.full((16,), float("nan"), device=device)
+        pws = torch.empty(L.ms_pose_scratch_bytes(N), dtype=torch.uint8, device=device)
+        _hip.check(L.ms_project_gaussians_bwd_pose(*args, _p(v_vm), _p(pws), pws.numel(), _hip.stream(device)))
+        torch.cuda.synchronize()
+        return out, v_vm
+
+    a, _ = run(False)
+    b, v1 = run(True)
+    _, v2_ = run(True)
+    for x, y in zip(a, b):
+        assert torch.equal(x, y)
+    assert torch.isfinite(v1).all() and torch.all(v1[12:] == 0) and torch.equal(v1, v2_)
+
+
+@pytest.mark.parametrize("degree", [0, 3])
+def test_sh_bwd_pose_bit_identical_and_deterministic(device, degree):
+    """k_sh_bwd<DEG, true>: v_coeffs / v_means3d exactly those of the pose-free call, v_campos the same bits twice and
+    with v_means3d NULL (the directional gradient is still formed)."""
+    L = _hip.lib()
+    N, K = 3000, 16
+    g = torch.Generator().manual_seed(6)
+    m3 = (torch.randn(N, 3, generator=g) * 2).to(device)
+    co = (torch.randn(N, K, 3, generator=g) * 0.3).to(device)
+    radii = torch.randint(0, 3, (N, 2), generator=g, dtype=torch.int32).to(device)
+    vcol = torch.randn(N, 3, generator=g).to(device)
+    cp = (0.3, -1.2, 4.0)
+    cols = torch.empty(N, 3, device=device)
+    _hip.check(L.ms_spherical_harmonics_fwd(N, K, degree, _p(m3), *cp, _p(co), _p(radii), 1, 0, _p(cols), _hip.stream(device)))
+
+    def run(pose, with_means=True):
+        vco, vme = torch.empty(N, K, 3, device=device), torch.empty(N, 3, device=device) if with_means else None
+        args = [N, K, degree, _p(m3), *cp, _p(co), _p(radii), 1, _p(cols), _p(vcol), _p(vco), _p(vme)]
+        if not pose:
+            _hip.check(L.ms_spherical_harmonics_bwd(*args, _hip.stream(device)))
+            torch.cuda.synchronize()
+            return vco, vme, None
+        vc = torch.full((3,), float("nan"), device=device)
+        pws = torch.empty(L.ms_pose_scratch_bytes(N), dtype=torch.uint8, device=device)
+        _hip.check(L.ms_spherical_harmonics_bwd_pose(*args, _p(vc), _p(pws), pws.numel(), _hip.stream(device)))
+        torch.cuda.synchronize()
+        return vco, vme, vc
+
+    a = run(False)
+    b = run(True)
+    c = run(True, with_means=False)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[0], c[0])
+    assert torch.isfinite(b[2]).all() and torch.equal(b[2], c[2])
+    # the definition: minus the sum of the directional means gradients, within float32 summation error
+    ref = -a[1].double().sum(0)
+    assert torch.allclose(b[2].double(), ref, rtol=1e-4, atol=1e-4 * float(a[1].abs().sum()))
+
+
+ROUTES = [dict(ts=16), dict(ts=16, bin_px=32, densify=True), dict(ts=16, C=4), dict(ts=8), dict(ts=16, stagewise=True),
+          dict(ts=16, stagewise=True, densify=True), dict(ts=16, sh=3), dict(ts=16, sh=2, stagewise=True)]
+
+
+def _step(device, sc, cam, route, pose, monkeypatch):
+    monkeypatch.delenv("MOJOSPLAT_TRAIN_BIN_PX", raising=False)
+    if route.get("bin_px"):
+        monkeypatch.setenv("MOJOSPLAT_TRAIN_BIN_PX", str(route["bin_px"]))
+    leaves = [sc[k].clone().requires_grad_(True) for k in NAMES]
+    pcam = _posed(cam, pose)
+    st = DensifyStats(leaves[0].shape[0], device) if route.get("densify") else None
+    img = render_gaussians_trainable(*leaves, pcam, tile_size=route["ts"], sh_degree=route.get("sh"),
+                                     stagewise=route.get("stagewise", False), densify=st)
+    v = torch.rand(img.shape, generator=torch.Generator().manual_seed(2)).to(device)
+    img.backward(v)
+    return img.detach(), [l.grad for l in leaves], st, pcam.view_matrix.grad
+
+
+@pytest.mark.parametrize("route", ROUTES, ids=lambda r: "-".join(f"{k}{v}" for k, v in r.items()))
+def test_every_route_pose_on_off(device, monkeypatch, route):
+    """End to end, pose on against pose off: the same image bit for bit, the same Gaussian gradients and statistics up
+    to the float-atomic rounding of the backward rasterisers' sums (which differs between ANY two steps), and a second
+    backward through the same graph (retain_graph) gives the same pose gradient to that rounding."""
+    sc, cam = _square_scene(device, C=route.get("C", 3), seed=21, sh=route.get("sh"))
+    img0, g0, st0, vg0 = _step(device, sc, cam, route, False, monkeypatch)
+    img1, g1, st1, vg1 = _step(device, sc, cam, route, True, monkeypatch)
+    assert vg0 is None and vg1 is not None and torch.isfinite(vg1).all() and vg1.abs().sum() > 0
+    assert torch.equal(img0, img1)
+    for name, a, b in zip(NAMES, g0, g1):
+        assert_grad_close(f"{route}/{name}", b, a, rel=1e-5)
+    if st0 is not None:
+        assert torch.equal(st0.count, st1.count) and torch.equal(st0.max_radii, st1.max_radii)
+        assert_grad_close(f"{route}/grad2d", st1.grad2d, st0.grad2d, rel=1e-5)
+        assert st1.count.sum() > 0
+    leaves = [sc[k].clone().requires_grad_(True) for k in NAMES]
+    pcam = _posed(cam)
+    img = render_gaussians_trainable(*leaves, pcam, tile_size=route["ts"], sh_degree=route.get("sh"),
+                                     stagewise=route.get("stagewise", False))
+    v = torch.rand(img.shape, generator=torch.Generator().manual_seed(2)).to(device)
+    r1 = torch.autograd.grad(img, pcam.view_matrix, v, retain_graph=True)[0]
+    r2 = torch.autograd.grad(img, pcam.view_matrix, v)[0]
+    assert_grad_close(f"{route}/retain_graph", r2, r1, rel=1e-5)
+    assert_grad_close(f"{route}/step", r1, vg1, rel=1e-5)
+
+
+@pytest.mark.parametrize("stagewise", [False, True])
+def test_empty_frame_gives_zero_pose_gradient(device, stagewise):
+    sc, cam = _square_scene(device, seed=23)
+    vm = cam.view_matrix.detach().clone()
+    vm[2, 3] = -50.0                              # every Gaussian behind the camera
+    pcam = Camera(R=vm[:3, :3], T=vm[:3, 3], H=cam.H, W=cam.W, fx=cam.fx, fy=cam.fy, cx=cam.cx, cy=cam.cy,
+                  view_matrix=vm.requires_grad_(True))
+    leaves = [sc[k].clone().requires_grad_(True) for k in NAMES]
+    img = render_gaussians_trainable(*leaves, pcam, stagewise=stagewise)
+    assert float(img.detach().abs().max()) == 0.0
+    img.sum().backward()
+    assert pcam.view_matrix.grad is not None and torch.equal(pcam.view_matrix.grad, torch.zeros_like(vm))
+
+
+def test_only_the_pose_requires_grad(device):
+    """render_gaussians takes the differentiable frame for a view matrix that requires grad alone."""
+    sc, cam = _square_scene(device, seed=24)
+    pcam = _posed(cam)
+    img = render_gaussians(*[sc[k] for k in NAMES], pcam)
+    assert img.requires_grad
+    img.square().sum().backward()
+    assert pcam.view_matrix.grad is not None and pcam.view_matrix.grad.abs().sum() > 0
+
+
+# ------------------------------------------------------------------ 4. the public surface
+def _f64_viewmat_grad(sc, cam, v_img):
+    """float64 dL/dviewmat of sum(image * v_img) on the HIP forward's visibility and 16-px binning."""
+    ts = 16
+    with torch.no_grad():
+        m2h, conh, deph, radh = project_gaussians_autograd(*[sc[k] for k in NAMES[:4]], cam)
+        ids, ranges = bin_gaussians_to_tiles_hip(m2h, radh, deph, ts, -(-cam.W // ts), -(-cam.H // ts))
+    rl = [sc[k].detach().cpu().double() for k in NAMES]
+    vm64 = cam.view_matrix.detach().cpu().double().requires_grad_(True)
+    rm2, rcon, _ = torch_oracle.project(rl[0], rl[1], rl[2], vm64, cam.fx, cam.fy, cam.cx, cam.cy, cam.W, cam.H)
+    rimg, _ = torch_oracle.rasterize(rm2, rcon, rl[4], rl[3], torch.zeros(3, dtype=torch.float64), ranges.cpu().to(torch.int32),
+                                     ids.cpu().to(torch.int32), cam.H, cam.W, ts)
+    (rimg * v_img.double().cpu()).sum().backward()
+    return vm64.grad
+
+
+def test_camera_R_T_and_look_at_eye_receive_gradients(device):
+    sc, cam = _square_scene(device, seed=25)
+    v = (torch.rand(cam.H, cam.W, 3, generator=torch.Generator().manual_seed(3)) - 0.4).to(device)
+    ref = _f64_viewmat_grad(sc, cam, v)
+    R = cam.R.detach().clone().requires_grad_(True)
+    T = cam.T.detach().clone().requires_grad_(True)
+    c = Camera(R=R, T=T, H=cam.H, W=cam.W, fx=cam.fx, fy=cam.fy, cx=cam.cx, cy=cam.cy)
+    (render_gaussians(*[sc[k] for k in NAMES], c) * v).sum().backward()
+    assert_grad_close("Camera.R", R.grad, ref[:3, :3], rel=2e-3)
+    assert_grad_close("Camera.T", T.grad, ref[:3, 3], rel=2e-3)
+    # look_at: the float64 chain of the reference view-matrix gradient through look_at's own Jacobian
+    eye = torch.tensor([0.0, 1.5, 5.0], device=device, requires_grad=True)
+    tgt, upv = torch.zeros(3, device=device), torch.tensor([0.0, 1.0, 0.0], device=device)
+    vm = look_at(eye, tgt, upv)
+    c = Camera(R=vm[:3, :3], T=vm[:3, 3], H=cam.H, W=cam.W, fx=cam.fx, fy=cam.fy, cx=cam.cx, cy=cam.cy, view_matrix=vm)
+    (render_gaussians(*[sc[k] for k in NAMES], c) * v).sum().backward()
+    eye64 = eye.detach().cpu().double().requires_grad_(True)
+    fwd = torch.nn.functional.normalize(-eye64, dim=0)
+    right = torch.nn.functional.normalize(torch.linalg.cross(fwd, upv.cpu().double()), dim=0)
+    Rt = torch.stack([right, torch.linalg.cross(right, fwd), fwd], 0)
+    vm64 = torch.cat([torch.cat([Rt, -(Rt @ eye64)[:, None]], 1), torch.tensor([[0.0, 0, 0, 1]], dtype=torch.float64)], 0)
+    (vm64 * ref).sum().backward()
+    assert_grad_close("look_at.eye", eye.grad, eye64.grad, rel=2e-3)
+
+
+# ------------------------------------------------------------------ 5. pose recovery
+def _se3_exp(xi):
+    """(6,) twist (rotation w, translation u) -> 4x4 rigid transform."""
+    A = torch.zeros(4, 4, dtype=xi.dtype, device=xi.device)
+    w, u = xi[:3], xi[3:]
+    A[0, 1], A[0, 2], A[1, 2] = -w[2], w[1], -w[0]
+    A[1, 0], A[2, 0], A[2, 1] = w[2], -w[1], w[0]
+    A[:3, 3] = u
+    return torch.linalg.matrix_exp(A)
+
+
+def _pose_error(vm, vm_true):
+    D = vm @ torch.linalg.inv(vm_true)
+    ang = torch.arccos(((D[:3, :3].trace() - 1) / 2).clamp(-1, 1))
+    return float(ang) + float(D[:3, 3].norm())
+
+
+def test_pose_recovery_with_adam(device):
+    torch.manual_seed(0)
+    sc, cam = randscene_v1(2000, 128, 128, ell=-3.0, seed=31, device=device)
+    vm_true = cam.view_matrix.detach().clone()
+    with torch.no_grad():
+        target = render_gaussians(*[sc[k] for k in NAMES], cam)
+    delta = _se3_exp(torch.tensor([0.02, -0.03, 0.015, 0.06, -0.04, 0.05], device=device))
+    vm0 = delta @ vm_true
+    xi = torch.zeros(6, device=device, requires_grad=True)
+    opt = torch.optim.Adam([xi], lr=2e-3)
+    err0 = _pose_error(vm0, vm_true)
+    for _ in range(150):
+        vm = _se3_exp(xi) @ vm0
+        c = Camera(R=vm[:3, :3], T=vm[:3, 3], H=cam.H, W=cam.W, fx=cam.fx, fy=cam.fy, cx=cam.cx, cy=cam.cy, view_matrix=vm)
+        loss = (render_gaussians(*[sc[k] for k in NAMES], c) - target).abs().mean()
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+    err = _pose_error((_se3_exp(xi) @ vm0).detach(), vm_true)
+    assert err < 0.5 * err0, (err0, err)
+
+
+# ------------------------------------------------------------------ 6. sharded
+def test_sharded_trainer_refuses_a_pose_that_requires_grad(device):
+    from mojosplat_amd.distributed import render_gaussians_trainable_sharded
+    sc, cam = _square_scene(device, seed=40)
+    with pytest.raises(ValueError, match="camera pose"):
+        render_gaussians_trainable_sharded(*[sc[k] for k in NAMES], _posed(cam), rehearse=(0, 1))
