@@ -23,6 +23,8 @@
  *   ms_densify_stats_update           (no reference counterpart)
  *   ms_*_pose, ms_pose_scratch_bytes  the gradient w.r.t. the camera pose (view matrix / camera centre) in the
  *                                     training backward (no reference counterpart; gsplat returns it)
+ *   ms_photometric_loss_*             the L1 + D-SSIM training loss, fused forward and backward (nothing in the
+ *                                     reference: it is forward-only, README.md:145; the CUDA stack's fused-ssim)
  *   ms_render_fwd_batch               the same for C cameras: the camera dimension of the reference's
  *                                     kernels (kernels/projection.mojo:32-37) that its wrappers pin to 1
  *
@@ -619,6 +621,30 @@ int ms_isect_tiles_emit_speculative(int64_t N, const float *means2d, const int32
                                     const int64_t *prev_info_host, int tight, int lazy,
                                     float depth_near, float depth_far, uint64_t *sort_keys,
                                     int32_t *flatten_ids, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Photometric loss of 3DGS training (csrc/loss.hip; the definition: mojosplat_amd/loss.py, photometric_loss_torch):
+ *   loss = (1 - lambda_dssim) * mean|img - target| + lambda_dssim * (1 - mean SSIM(img, target)),
+ * SSIM per channel under the 11x11 Gaussian window (sigma 1.5) with 5 pixels of zero padding, C1 = 0.01^2, C2 = 0.03^2.
+ * Replaces nothing in the reference (it is forward-only, README.md:145); the CUDA stack's fused-ssim extension.
+ *   img, target : f32[B,H,W,C], channel innermost -- the tensor ms_render_fwd writes (B = 1); C in 1..4.
+ *   workspace   : ms_photometric_loss_workspace_bytes(B, H, W, C, keep_for_backward) bytes (0: bad sizes).  With
+ *                 keep_for_backward != 0 the forward leaves three derivative planes there (12 bytes per image element) and
+ *                 the SAME workspace, untouched, goes to ms_photometric_loss_bwd; with 0 it holds partial sums only.
+ *   out3        : f32[3] (DEVICE) = {loss, l1, ssim}, overwritten.
+ *   v_loss      : f32[1] (DEVICE): dL/dloss, read by the kernel -- never brought to the host.
+ *   v_img       : f32[B,H,W,C] = dL/dimg, overwritten (target is data: no gradient).
+ * Two launches forward, one backward, on `stream`; no host synchronisation, no allocation, no float atomics: the same
+ * inputs give the same bits on every run.  B*H*W*C above 2^31 - 1 is refused (MS_ERR_TOO_LARGE); null pointers, sizes
+ * <= 0, C outside 1..4, lambda_dssim outside [0, 1] -> MS_ERR_INVALID_ARG, a short workspace -> MS_ERR_WORKSPACE, all
+ * before any device work.
+ * ------------------------------------------------------------------------------------- */
+size_t ms_photometric_loss_workspace_bytes(int B, int H, int W, int C, int keep_for_backward);
+int ms_photometric_loss_fwd(int B, int H, int W, int C, const float *img, const float *target, float lambda_dssim,
+                            void *workspace, size_t workspace_bytes, int keep_for_backward, float *out3, void *stream);
+int ms_photometric_loss_bwd(int B, int H, int W, int C, const float *img, const float *target, float lambda_dssim,
+                            const void *workspace, size_t workspace_bytes, const float *v_loss, float *v_img,
+                            void *stream);
 
 #ifdef __cplusplus
 }

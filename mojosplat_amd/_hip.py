@@ -136,6 +136,13 @@ _SIGNATURES["ms_render_band_begin"] = (c_int, [ctypes.POINTER(BandFrame), ctypes
 _SIGNATURES["ms_render_band_finish"] = (c_int, [ctypes.POINTER(BandFrame), ctypes.POINTER(BandLane), c_void_p, c_int,
                                                ctypes.POINTER(c_int64)])
 
+# the L1 + D-SSIM training loss (csrc/loss.hip): B, H, W, C, img, target, lambda, workspace, its bytes, ...
+_SIGNATURES["ms_photometric_loss_workspace_bytes"] = (c_size_t, [c_int, c_int, c_int, c_int, c_int])
+_SIGNATURES["ms_photometric_loss_fwd"] = (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_size_t,
+                                                  c_int, c_void_p, c_void_p])
+_SIGNATURES["ms_photometric_loss_bwd"] = (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_size_t,
+                                                  c_void_p, c_void_p, c_void_p])
+
 # entry points added after ABI v1's first cut; bound when present
 _OPTIONAL = {}
 
