@@ -25,6 +25,9 @@
  *                                     training backward (no reference counterpart; gsplat returns it)
  *   ms_photometric_loss_*             the L1 + D-SSIM training loss, fused forward and backward (nothing in the
  *                                     reference: it is forward-only, README.md:145; the CUDA stack's fused-ssim)
+ *   ms_adam_step                      the Adam update of up to 8 parameter tensors in one launch, optionally masked by
+ *                                     the view's visibility (nothing in the reference: it is forward-only and updates no
+ *                                     parameter; the CUDA stack's torch.optim.Adam(fused=True), gsplat's SelectiveAdam)
  *   ms_render_fwd_batch               the same for C cameras: the camera dimension of the reference's
  *                                     kernels (kernels/projection.mojo:32-37) that its wrappers pin to 1
  *
@@ -58,8 +61,8 @@
 extern "C" {
 #endif
 
-#define MS_ABI_VERSION 4   /* 2: ms_render_bwd takes the frame's image (render_colors); 3: ms_render_redo_counts, the band-frame pair, ms_scene_prepare;
-                              4: the pose-gradient entry points (ms_pose_scratch_bytes, ms_*_pose) */
+#define MS_ABI_VERSION 5   /* 2: ms_render_bwd takes the frame's image (render_colors); 3: ms_render_redo_counts, the band-frame pair, ms_scene_prepare;
+                              4: the pose-gradient entry points (ms_pose_scratch_bytes, ms_*_pose); 5: ms_adam_step */
 
 typedef enum ms_status {
     MS_OK = 0,
@@ -645,6 +648,45 @@ int ms_photometric_loss_fwd(int B, int H, int W, int C, const float *img, const 
 int ms_photometric_loss_bwd(int B, int H, int W, int C, const float *img, const float *target, float lambda_dssim,
                             const void *workspace, size_t workspace_bytes, const float *v_loss, float *v_img,
                             void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Optimiser step of 3DGS training (csrc/adam.hip; the definition: mojosplat_amd/optim.py, GaussianAdam with
+ * backend="torch"): Adam, per element and in float32,
+ *   m' = beta1 m + (1 - beta1) g,  v' = beta2 v + (1 - beta2) g g,
+ *   p' = p - (lr / bias_correction1) m' / (sqrt(v') / bias_correction2_sqrt + eps)
+ * -- torch.optim.Adam without amsgrad, weight decay or maximize -- for n_tensors (1..MS_ADAM_MAX_TENSORS) parameter tensors
+ * in ONE launch whose workgroups are shared among the tensors in proportion to their sizes.
+ * Replaces nothing in the reference (it is forward-only and updates no parameter); the CUDA stack's
+ * torch.optim.Adam(fused=True) and, with a mask, gsplat's SelectiveAdam.
+ *   tensors     : HOST array of n_tensors records, read during the call (the kernel receives what it needs by value):
+ *                   param, exp_avg, exp_avg_sq : f32[rows, width], contiguous, updated in place
+ *                   grad                       : f32[rows, width], contiguous, read
+ *                   rows, width                : > 0, rows * width < 2^31; width = elements per row (3 for means, 1 for
+ *                                                opacities, 48 for SH degree 3 ...)
+ *                   lr, beta1, beta2, eps      : lr >= 0 and finite, betas in [0, 1), eps > 0
+ *                   bias_correction1           : 1 - beta1^t,        in (0, 1] | computed by the caller in double from ITS
+ *                   bias_correction2_sqrt      : sqrt(1 - beta2^t),  in (0, 1] | step count t: the device keeps no count
+ *                 16-byte aligned pointers get 16-byte loads and stores; others are served element by element.
+ *   visible     : u8[visible_rows] or NULL.  A row (of every tensor) whose byte is 0 is neither read nor written: its param
+ *                 and moments stay bit for bit.  Rows with a non-zero byte get exactly the bits the NULL call gives them.
+ *                 With a mask every tensor must have rows == visible_rows; without one visible_rows is ignored.
+ * One launch on `stream` (a hipStream_t), no host synchronisation, no allocation, no atomics: the same inputs give the same
+ * bits on every run.  IEEE sqrt and division, no contraction.  n_tensors outside 1..8, a null pointer, rows or width <= 0,
+ * a negative or non-finite lr, a beta outside [0, 1), eps <= 0 or NaN, a bias correction outside (0, 1], a row count that
+ * differs from the mask's -> MS_ERR_INVALID_ARG; a tensor of 2^31 elements or more -> MS_ERR_TOO_LARGE; all before any
+ * device work.
+ * ------------------------------------------------------------------------------------- */
+#define MS_ADAM_MAX_TENSORS 8
+typedef struct ms_adam_tensor {
+    float *param;
+    const float *grad;
+    float *exp_avg;
+    float *exp_avg_sq;
+    int64_t rows, width;
+    double lr, beta1, beta2, eps;
+    double bias_correction1, bias_correction2_sqrt;
+} ms_adam_tensor;
+int ms_adam_step(int n_tensors, const ms_adam_tensor *tensors, const uint8_t *visible, int64_t visible_rows, void *stream);
 
 #ifdef __cplusplus
 }

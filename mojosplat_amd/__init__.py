@@ -13,6 +13,7 @@ from .render import render_gaussians, render_gaussians_batch, TILE_SIZE
 from .sh import evaluate_sh
 from .densify import DensifyStats
 from .loss import photometric_loss, ssim
+from .optim import GaussianAdam
 
 
 def prepare_scene(*args, **kw):
@@ -27,4 +28,4 @@ def release_scratch():
     _release()
 
 __all__ = ["Camera", "look_at", "project_gaussians", "bin_gaussians_to_tiles",
-           "rasterize_gaussians", "render_gaussians", "render_gaussians_batch", "evaluate_sh", "DensifyStats", "photometric_loss", "ssim", "release_scratch", "prepare_scene", "TILE_SIZE"]
+           "rasterize_gaussians", "render_gaussians", "render_gaussians_batch", "evaluate_sh", "DensifyStats", "photometric_loss", "ssim", "GaussianAdam", "release_scratch", "prepare_scene", "TILE_SIZE"]

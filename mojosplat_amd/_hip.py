@@ -18,7 +18,7 @@ _LIB_PATH = os.environ.get("MOJOSPLAT_HIP_LIB") or \
     os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libmojosplat_hip.so")
 _lib = None
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 # name -> (restype, argtypes); mirrors include/mojosplat_hip.h one to one
 _SIGNATURES = {
@@ -142,6 +142,20 @@ _SIGNATURES["ms_photometric_loss_fwd"] = (c_int, [c_int, c_int, c_int, c_int, c_
                                                   c_int, c_void_p, c_void_p])
 _SIGNATURES["ms_photometric_loss_bwd"] = (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_size_t,
                                                   c_void_p, c_void_p, c_void_p])
+
+
+
+class AdamTensor(ctypes.Structure):
+    """ms_adam_tensor (include/mojosplat_hip.h): one parameter tensor of an ms_adam_step call."""
+    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
+                ("rows", c_int64), ("width", c_int64), ("lr", ctypes.c_double), ("beta1", ctypes.c_double),
+                ("beta2", ctypes.c_double), ("eps", ctypes.c_double), ("bias_correction1", ctypes.c_double),
+                ("bias_correction2_sqrt", ctypes.c_double)]
+
+
+ADAM_MAX_TENSORS = 8
+# the Adam step (csrc/adam.hip): n_tensors, the records (host), the visibility mask or None, its rows, stream
+_SIGNATURES["ms_adam_step"] = (c_int, [c_int, ctypes.POINTER(AdamTensor), c_void_p, c_int64, c_void_p])
 
 # entry points added after ABI v1's first cut; bound when present
 _OPTIONAL = {}
