@@ -28,6 +28,8 @@
  *   ms_adam_step                      the Adam update of up to 8 parameter tensors in one launch, optionally masked by
  *                                     the view's visibility (nothing in the reference: it is forward-only and updates no
  *                                     parameter; the CUDA stack's torch.optim.Adam(fused=True), gsplat's SelectiveAdam)
+ *   ms_densify_classify,              the densification step (clone, split, prune) over every parameter tensor and its Adam
+ *   ms_densify_move                   moments (nothing in the reference; the CUDA stack's gsplat DefaultStrategy)
  *   ms_render_fwd_batch               the same for C cameras: the camera dimension of the reference's
  *                                     kernels (kernels/projection.mojo:32-37) that its wrappers pin to 1
  *
@@ -62,7 +64,8 @@ extern "C" {
 #endif
 
 #define MS_ABI_VERSION 5   /* 2: ms_render_bwd takes the frame's image (render_colors); 3: ms_render_redo_counts, the band-frame pair, ms_scene_prepare;
-                              4: the pose-gradient entry points (ms_pose_scratch_bytes, ms_*_pose); 5: ms_adam_step */
+                              4: the pose-gradient entry points (ms_pose_scratch_bytes, ms_*_pose); 5: ms_adam_step
+                              (the ms_densify_* entry points were added under 5: new symbols, nothing existing changed) */
 
 typedef enum ms_status {
     MS_OK = 0,
@@ -687,6 +690,64 @@ typedef struct ms_adam_tensor {
     double bias_correction1, bias_correction2_sqrt;
 } ms_adam_tensor;
 int ms_adam_step(int n_tensors, const ms_adam_tensor *tensors, const uint8_t *visible, int64_t visible_rows, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * The densification step of 3DGS training: clone, split and prune (csrc/densify.hip; the definition:
+ * mojosplat_amd/refine.py, densify_and_prune_torch).  Replaces nothing in the reference (it is forward-only); the CUDA
+ * stack's gsplat DefaultStrategy (duplicate, split, remove).  Two calls with the caller's ONE host read between them,
+ * because the outputs have to be allocated:
+ *
+ * ms_densify_classify  decides every Gaussian in float32 (IEEE division, no contraction, scale tests in log space) and
+ *                      scans the per-workgroup counts.  With g = grad2d / max(count, 1), smax = max(scales row):
+ *                        high  = g > grow_grad2d          small    = smax <= log_grow
+ *                        clone = high & small             split    = (high & !small) | (max_radii > grow_radius)
+ *                        lowop = opacity < thr_opa        big      = (smax > log_big) | (max_radii > prune_radius)
+ *                                                         childbig = (smax - float32(log 1.6) > log_big) | (max_radii > prune_radius)
+ *                      flag bit 0: an original stays (!split & !lowop & !big); bit 1: a clone appears (clone & !lowop & !big);
+ *                      bit 2: two children appear (split & !lowop & !childbig).
+ *   grad2d, count, max_radii, opacities : f32[N];  scales : f32[N, 3], log space
+ *   rules      : HOST, the thresholds, each rounded to float32 once by the caller; +inf switches a rule off; none is NaN
+ *   workspace  : ms_densify_workspace_bytes(N) bytes, 16-byte aligned: the flag bytes and the scanned counts; it is what
+ *                ms_densify_move reads
+ *   totals     : i64[4], out: originals kept, clones, split rows (each leaves two children), source rows that leave nothing
+ * ms_densify_move      writes the output rows -- [kept originals | clones | first children | second children], each
+ *                      segment in ascending source row -- of up to MS_DENSIFY_MAX_TENSORS tensors per call (more: call
+ *                      again with the next records) in one launch.
+ *   n_kept, n_cloned, n_split : totals[0..2] of the classify call on the same workspace
+ *   tensors    : HOST array of n_tensors records: src f32[N, width] -> dst f32[n_kept + n_cloned + 2 n_split, width], and kind:
+ *                  MS_DENSIFY_COPY   every output row is a bit copy of its source row
+ *                  MS_DENSIFY_MEAN   (width 3) originals and clones copied; the children's rows are the row outputs' below
+ *                  MS_DENSIFY_SCALE  (width 3) children get src - float32(log 1.6), one float32 subtraction
+ *                  MS_DENSIFY_MOMENT originals copied; clones' and children's rows are written as ZEROS
+ *                16-byte loads and stores when width is a multiple of 4 and both pointers are 16-byte aligned, dwords otherwise.
+ *   means3d, scales, quats (f32[N,3], [N,3], [N,4] wxyz), noise (f32[2, N, 3]), out_means3d (the MEAN record's dst), source
+ *   (i64[rows out], each output row's source row): the row outputs, all six or all NULL.  Given, the call also writes `source`
+ *   and both children's means, mean + R(q / |q|) (exp(scales) * noise[c]), c = 0 / 1; noise is read for split rows only.
+ * No atomics, order-preserving, the same inputs give the same bits on every run; no host synchronisation, no allocation.
+ * N = 0 (and, for the move, no output row) is a no-op.  A negative size, a null pointer, a NaN threshold, a kind out of range,
+ * a MEAN or SCALE record whose width is not 3 -> MS_ERR_INVALID_ARG; a short workspace -> MS_ERR_WORKSPACE; a tensor of
+ * 2^31 elements or more before or after -> MS_ERR_TOO_LARGE; all before any device work.
+ * ------------------------------------------------------------------------------------- */
+#define MS_DENSIFY_ROWS 256          /* Gaussians per workgroup of the classify and move kernels */
+#define MS_DENSIFY_SCAN_SPAN 512     /* workgroup counts the scan kernel takes in one pass of its lanes */
+#define MS_DENSIFY_MAX_TENSORS 16
+typedef enum ms_densify_kind { MS_DENSIFY_COPY = 0, MS_DENSIFY_MEAN = 1, MS_DENSIFY_SCALE = 2, MS_DENSIFY_MOMENT = 3 } ms_densify_kind;
+typedef struct ms_densify_rules {
+    float grow_grad2d, log_grow, grow_radius, thr_opa, log_big, prune_radius;
+} ms_densify_rules;
+typedef struct ms_densify_tensor {
+    const float *src;
+    float *dst;
+    int64_t width;
+    int kind;
+} ms_densify_tensor;
+size_t ms_densify_workspace_bytes(int64_t N);
+int ms_densify_classify(int64_t N, const float *grad2d, const float *count, const float *max_radii, const float *scales,
+                        const float *opacities, const ms_densify_rules *rules, void *workspace, size_t workspace_bytes,
+                        int64_t *totals, void *stream);
+int ms_densify_move(int64_t N, int64_t n_kept, int64_t n_cloned, int64_t n_split, const void *workspace, size_t workspace_bytes,
+                    int n_tensors, const ms_densify_tensor *tensors, const float *means3d, const float *scales,
+                    const float *quats, const float *noise, float *out_means3d, int64_t *source, void *stream);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,7 @@ from .sh import evaluate_sh
 from .densify import DensifyStats
 from .loss import photometric_loss, ssim
 from .optim import GaussianAdam
+from .refine import densify_and_prune, reset_opacities, DensifyResult
 
 
 def prepare_scene(*args, **kw):
@@ -28,4 +29,4 @@ def release_scratch():
     _release()
 
 __all__ = ["Camera", "look_at", "project_gaussians", "bin_gaussians_to_tiles",
-           "rasterize_gaussians", "render_gaussians", "render_gaussians_batch", "evaluate_sh", "DensifyStats", "photometric_loss", "ssim", "GaussianAdam", "release_scratch", "prepare_scene", "TILE_SIZE"]
+           "rasterize_gaussians", "render_gaussians", "render_gaussians_batch", "evaluate_sh", "DensifyStats", "photometric_loss", "ssim", "GaussianAdam", "densify_and_prune", "reset_opacities", "DensifyResult", "release_scratch", "prepare_scene", "TILE_SIZE"]

@@ -157,6 +157,30 @@ ADAM_MAX_TENSORS = 8
 # the Adam step (csrc/adam.hip): n_tensors, the records (host), the visibility mask or None, its rows, stream
 _SIGNATURES["ms_adam_step"] = (c_int, [c_int, ctypes.POINTER(AdamTensor), c_void_p, c_int64, c_void_p])
 
+
+class DensifyRules(ctypes.Structure):
+    """ms_densify_rules (include/mojosplat_hip.h): the float32 thresholds of ms_densify_classify; +inf = the rule is off."""
+    _fields_ = [("grow_grad2d", c_float), ("log_grow", c_float), ("grow_radius", c_float), ("thr_opa", c_float),
+                ("log_big", c_float), ("prune_radius", c_float)]
+
+
+class DensifyTensor(ctypes.Structure):
+    """ms_densify_tensor: one tensor of an ms_densify_move call."""
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("width", c_int64), ("kind", c_int)]
+
+
+DENSIFY_ROWS = 256            # MS_DENSIFY_ROWS: Gaussians per workgroup of the classify and move kernels
+DENSIFY_SCAN_SPAN = 512       # MS_DENSIFY_SCAN_SPAN: workgroup counts per pass of the scan kernel's lanes
+DENSIFY_MAX_TENSORS = 16
+DENSIFY_COPY, DENSIFY_MEAN, DENSIFY_SCALE, DENSIFY_MOMENT = range(4)
+# the densification step (csrc/densify.hip): classify + scan, then the table-driven move
+_SIGNATURES["ms_densify_workspace_bytes"] = (c_size_t, [c_int64])
+_SIGNATURES["ms_densify_classify"] = (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              ctypes.POINTER(DensifyRules), c_void_p, c_size_t, c_void_p, c_void_p])
+_SIGNATURES["ms_densify_move"] = (c_int, [c_int64, c_int64, c_int64, c_int64, c_void_p, c_size_t, c_int,
+                                          ctypes.POINTER(DensifyTensor), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p])
+
 # entry points added after ABI v1's first cut; bound when present
 _OPTIONAL = {}
 

@@ -254,6 +254,18 @@ class GaussianAdam(torch.optim.Optimizer):
                     st[k] = torch.cat([st[k][idx], z]).contiguous()
                 self.state[new] = st
 
+    def _adopt(self, new_params, new_moments):
+        """relocate's hand-over with ready-made moments (refine.py, backend="hip", which has checked everything): group
+        ``name``'s parameter becomes ``new_params[name]``, its moments ``new_moments[name] = [exp_avg, exp_avg_sq]``; a
+        parameter without state stays without.  ``step`` is kept."""
+        for g in self.param_groups:
+            (old,), new = g["params"], new_params[g["name"]]
+            st = self.state.pop(old, None)
+            g["params"] = [new]
+            if st:
+                st["exp_avg"], st["exp_avg_sq"] = new_moments[g["name"]]
+                self.state[new] = st
+
     @torch.no_grad()
     def zero_state(self, name):
         """Zero the moments of group ``name`` (3DGS's opacity reset); ``step`` is kept."""
