@@ -30,6 +30,8 @@
  *                                     parameter; the CUDA stack's torch.optim.Adam(fused=True), gsplat's SelectiveAdam)
  *   ms_densify_classify,              the densification step (clone, split, prune) over every parameter tensor and its Adam
  *   ms_densify_move                   moments (nothing in the reference; the CUDA stack's gsplat DefaultStrategy)
+ *   ms_mcmc_sample, ms_mcmc_apply,    the MCMC strategy: relocate dead Gaussians, grow, perturb the means (nothing in the
+ *   ms_mcmc_noise                     reference; the CUDA stack's gsplat MCMCStrategy)
  *   ms_render_fwd_batch               the same for C cameras: the camera dimension of the reference's
  *                                     kernels (kernels/projection.mojo:32-37) that its wrappers pin to 1
  *
@@ -65,7 +67,7 @@ extern "C" {
 
 #define MS_ABI_VERSION 5   /* 2: ms_render_bwd takes the frame's image (render_colors); 3: ms_render_redo_counts, the band-frame pair, ms_scene_prepare;
                               4: the pose-gradient entry points (ms_pose_scratch_bytes, ms_*_pose); 5: ms_adam_step
-                              (the ms_densify_* entry points were added under 5: new symbols, nothing existing changed) */
+                              (the ms_densify_* and ms_mcmc_* entry points were added under 5: new symbols, nothing existing changed) */
 
 typedef enum ms_status {
     MS_OK = 0,
@@ -748,6 +750,68 @@ int ms_densify_classify(int64_t N, const float *grad2d, const float *count, cons
 int ms_densify_move(int64_t N, int64_t n_kept, int64_t n_cloned, int64_t n_split, const void *workspace, size_t workspace_bytes,
                     int n_tensors, const ms_densify_tensor *tensors, const float *means3d, const float *scales,
                     const float *quats, const float *noise, float *out_means3d, int64_t *source, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * The 3DGS-MCMC strategy (csrc/mcmc.hip; the definition: mojosplat_amd/mcmc.py, relocate_dead_torch, grow_torch,
+ * inject_noise_torch).  Replaces nothing in the reference (it is forward-only); the CUDA stack's gsplat MCMCStrategy.
+ * Every call enqueues on `stream` and returns: no host synchronisation, no allocation.  The only atomics are integer ones
+ * (the draws of each source are counted; a count does not depend on the order), so the same inputs give the same bits.
+ *
+ * ms_mcmc_sample   classifies, weighs, scans and draws.  A row is dead when !(opacities[i] > thr) on the STORED value (a NaN
+ *                  is dead); its weight is 0, a live row's is round(o 2^24) with o = opacities[i] (logit = 0) or its sigmoid
+ *                  (logit = 1).  cum = the inclusive int64 scan, total = cum[N - 1].  Draw j: t = min(floor(draws[j] * total),
+ *                  total - 1) in double, sampled[j] = the first row with cum > t (never a zero-weight row); with sampled_in
+ *                  the draw is sampled_in[j] instead.  A draw whose source is out of range or dead is NOT applied:
+ *                  sampled[j] = -1.
+ *   grow = 0 (relocation): n_draws == N; the dead rows in ascending order are targets[0 .. n), n = their number (0 when
+ *                  total == 0); sampled and targets hold -1 from n on; *n_out = n (device, may be NULL).
+ *   grow = 1     : every one of the n_draws draws is made, targets[j] = N + j, *n_out = n_draws; with total == 0 no draw is
+ *                  applied.
+ *   opacities : f32[N];  thr : the threshold, rounded to float32 once by the caller (its logit with logit = 1)
+ *   draws     : f64[n_draws], uniform in [0, 1), or NULL when sampled_in i64[n_draws] is given
+ *   workspace : ms_mcmc_workspace_bytes(N) bytes, 16-byte aligned; it is what ms_mcmc_apply reads
+ *   sampled, targets : i64[n_draws], out
+ * ms_mcmc_apply    moves.  With values given (opacities, scales, binom: all or none -- the FIRST call after a sample), every
+ *                  row's new stored opacity and scales are first computed from the old ones into the workspace, before any
+ *                  row is written: a row drawn c > 0 times, n = min(c + 1, MS_MCMC_MAX_RATIO), gets
+ *                    o' = -expm1(log1p(-o) / n),  D = sum_b binom[n - 1][b] o'^(b + 1),  scales += log(o / D),
+ *                    opacity = clamp(o', min_opacity, 1 - 1e-7) (stored as its logit with logit = 1)
+ *                  evaluated in double; a row nobody drew keeps its values.  Then, for every applied draw and every record,
+ *                  in place: MS_MCMC_COPY row target <- row source; MS_MCMC_OPACITY (width 1) and MS_MCMC_SCALE (width 3)
+ *                  source and target <- the new values; MS_MCMC_MOMENT source and target <- 0.  With grow = 1 the target of a
+ *                  draw that was not applied becomes a copy of row 0 (and a MOMENT row of zeros).  Up to
+ *                  MS_MCMC_MAX_TENSORS records per call (more: call again with the next records and no values).
+ *   n_rows    : rows of every tensor: N, or N + n_draws after a grow (rows [0, N) filled by the caller)
+ *   binom     : f32[51 * 51], binom[n - 1][b] = (-1)^b C(n, b + 1) / sqrt(b + 1) (0 for b >= n), formed in double and rounded
+ *               once by the caller
+ *   tensors   : HOST array of n_tensors records: base f32[n_rows, width] and kind.  16-byte accesses when width is a multiple
+ *               of 4 and base is 16-byte aligned, dwords otherwise.
+ * ms_mcmc_noise    means3d += R (exp(2 scales) * (R^T v)) = Sigma v with R = R(quats / |quats|) (wxyz),
+ *                  v = noise * gate * step, gate = 1 / (1 + exp(-k ((1 - o) - x0))), o as above; float32, IEEE division and
+ *                  sqrt, no contraction.  means3d, scales, noise : f32[N,3]; quats : f32[N,4]; opacities : f32[N].
+ * N = 0 (and, for sample and apply, n_draws = 0) is a no-op.  A null pointer, a negative size, a misaligned pointer (float: 4
+ * bytes, double and int64: 8, workspace: 16), a NaN threshold or step, a kind out of range, an OPACITY or SCALE record of
+ * another width, min_opacity outside (0, 1) -> MS_ERR_INVALID_ARG; a short workspace -> MS_ERR_WORKSPACE; a tensor of 2^31
+ * elements or more -> MS_ERR_TOO_LARGE; all before any device work.
+ * ------------------------------------------------------------------------------------- */
+#define MS_MCMC_ROWS 256             /* Gaussians (or draws) per workgroup */
+#define MS_MCMC_MAX_RATIO 51         /* the relocation formula's largest n; the binomial table's side */
+#define MS_MCMC_MAX_TENSORS 16
+typedef enum ms_mcmc_kind { MS_MCMC_COPY = 0, MS_MCMC_OPACITY = 1, MS_MCMC_SCALE = 2, MS_MCMC_MOMENT = 3 } ms_mcmc_kind;
+typedef struct ms_mcmc_tensor {
+    float *base;
+    int64_t width;
+    int kind;
+} ms_mcmc_tensor;
+size_t ms_mcmc_workspace_bytes(int64_t N);
+int ms_mcmc_sample(int64_t N, const float *opacities, int logit, float thr, int64_t n_draws, int grow, const double *draws,
+                   const int64_t *sampled_in, void *workspace, size_t workspace_bytes, int64_t *sampled, int64_t *targets,
+                   int64_t *n_out, void *stream);
+int ms_mcmc_apply(int64_t N, int64_t n_draws, int64_t n_rows, int grow, void *workspace, size_t workspace_bytes,
+                  const int64_t *sampled, const int64_t *targets, int n_tensors, const ms_mcmc_tensor *tensors,
+                  const float *opacities, const float *scales, const float *binom, int logit, double min_opacity, void *stream);
+int ms_mcmc_noise(int64_t N, float *means3d, const float *scales, const float *quats, const float *opacities,
+                  const float *noise, int logit, float step, float k, float x0, void *stream);
 
 #ifdef __cplusplus
 }

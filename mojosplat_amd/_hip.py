@@ -181,6 +181,26 @@ _SIGNATURES["ms_densify_move"] = (c_int, [c_int64, c_int64, c_int64, c_int64, c_
                                           ctypes.POINTER(DensifyTensor), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p])
 
+
+class McmcTensor(ctypes.Structure):
+    """ms_mcmc_tensor: one tensor of an ms_mcmc_apply call, updated in place."""
+    _fields_ = [("base", c_void_p), ("width", c_int64), ("kind", c_int)]
+
+
+MCMC_ROWS = 256               # MS_MCMC_ROWS: Gaussians (or draws) per workgroup
+MCMC_MAX_RATIO = 51           # MS_MCMC_MAX_RATIO: the relocation formula's largest n
+MCMC_MAX_TENSORS = 16
+MCMC_COPY, MCMC_OPACITY, MCMC_SCALE, MCMC_MOMENT = range(4)
+# the MCMC strategy (csrc/mcmc.hip): sample (classify, scan, draw), the table-driven apply, the noise step
+_SIGNATURES["ms_mcmc_workspace_bytes"] = (c_size_t, [c_int64])
+_SIGNATURES["ms_mcmc_sample"] = (c_int, [c_int64, c_void_p, c_int, c_float, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                         c_size_t, c_void_p, c_void_p, c_void_p, c_void_p])
+_SIGNATURES["ms_mcmc_apply"] = (c_int, [c_int64, c_int64, c_int64, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_int,
+                                        ctypes.POINTER(McmcTensor), c_void_p, c_void_p, c_void_p, c_int, ctypes.c_double,
+                                        c_void_p])
+_SIGNATURES["ms_mcmc_noise"] = (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float,
+                                        c_float, c_void_p])
+
 # entry points added after ABI v1's first cut; bound when present
 _OPTIONAL = {}
 

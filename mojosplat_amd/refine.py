@@ -30,7 +30,7 @@ radius for the prune test).  A clone or an original is a bit copy of every tenso
 
 The schedule stays with the caller: when to refine, when the screen-size rules stop, when the too-big rule starts
 counting -- a rule passed as ``None`` is off.  Not covered: absgrad, gsplat's ``revised_opacity``, a cap on the Gaussian
-count, the MCMC strategy, the sharded trainer, graph capture, float16 parameters.
+count (mcmc.py's ``grow`` has one), the sharded trainer, graph capture, float16 parameters.
 """
 import ctypes
 import math
@@ -105,9 +105,8 @@ def child_means_torch(means3d, scales, quats, noise):
     return means3d + (R * v.unsqueeze(-2)).sum(-1)
 
 
-def _validate(params, stats, opt, noise, opacity_space, backend):
-    """Every check of densify_and_prune; -> (N, device).  Raises ValueError; changes nothing."""
-    from .optim import GaussianAdam, _check_hip_params
+def _validate_params(params, opacity_space, backend):
+    """The checks of the scene dict itself (densify_and_prune and mcmc.py share them); -> (N, device)."""
     if backend not in ("hip", "torch"):
         raise ValueError(f"Invalid backend: {backend!r} (\"hip\" or \"torch\")")
     if opacity_space not in ("linear", "logit"):
@@ -131,12 +130,12 @@ def _validate(params, stats, opt, noise, opacity_space, backend):
             raise ValueError(f"parameter {n!r} has shape {tuple(params[n].shape)}, expected {shape}")
     if tuple(params["opacities"].shape) not in ((N,), (N, 1)):
         raise ValueError(f"parameter 'opacities' has shape {tuple(params['opacities'].shape)}, expected ({N},) or ({N}, 1)")
-    if not isinstance(stats, DensifyStats):
-        raise ValueError("stats must be a DensifyStats")
-    stats.check(N, dev)
-    if noise is not None:
-        if not isinstance(noise, torch.Tensor) or tuple(noise.shape) != (2, N, 3) or noise.dtype != torch.float32 or noise.device != dev:
-            raise ValueError(f"noise must be a float32 tensor of shape (2, {N}, 3) on {dev}")
+    return N, dev
+
+
+def _validate_opt(params, opt):
+    """opt is None or a GaussianAdam over exactly the tensors of params."""
+    from .optim import GaussianAdam
     if opt is not None:
         if not isinstance(opt, GaussianAdam):
             raise ValueError("opt must be a GaussianAdam (or None)")
@@ -144,12 +143,30 @@ def _validate(params, stats, opt, noise, opacity_space, backend):
         if sorted(names) != sorted(params) or any(len(g["params"]) != 1 or g["params"][0] is not params[g["name"]]
                                                   for g in opt.param_groups):
             raise ValueError(f"opt's groups {names} are not exactly the tensors of params {list(params)}")
+
+
+def _validate_hip(params, opt, dev):
+    """What backend="hip" asks of the parameters and of opt's moments."""
+    from .optim import _check_hip_params
+    _check_hip_params(list(params.items()))
+    for n, p in params.items():
+        st = opt.state.get(p) if opt is not None else None
+        if st and any(st[k].device != dev for k in ("exp_avg", "exp_avg_sq")):
+            raise ValueError(f"backend='hip': the moments of {n!r} are not on {dev}")
+
+
+def _validate(params, stats, opt, noise, opacity_space, backend):
+    """Every check of densify_and_prune; -> (N, device).  Raises ValueError; changes nothing."""
+    N, dev = _validate_params(params, opacity_space, backend)
+    if not isinstance(stats, DensifyStats):
+        raise ValueError("stats must be a DensifyStats")
+    stats.check(N, dev)
+    if noise is not None:
+        if not isinstance(noise, torch.Tensor) or tuple(noise.shape) != (2, N, 3) or noise.dtype != torch.float32 or noise.device != dev:
+            raise ValueError(f"noise must be a float32 tensor of shape (2, {N}, 3) on {dev}")
+    _validate_opt(params, opt)
     if backend == "hip":
-        _check_hip_params(list(params.items()))
-        for n, p in params.items():
-            st = opt.state.get(p) if opt is not None else None
-            if st and any(st[k].device != dev for k in ("exp_avg", "exp_avg_sq")):
-                raise ValueError(f"backend='hip': the moments of {n!r} are not on {dev}")
+        _validate_hip(params, opt, dev)
         if noise is not None and not noise.is_contiguous():
             raise ValueError("backend='hip': noise must be contiguous")
     return N, dev
