@@ -32,6 +32,8 @@
  *   ms_densify_move                   moments (nothing in the reference; the CUDA stack's gsplat DefaultStrategy)
  *   ms_mcmc_sample, ms_mcmc_apply,    the MCMC strategy: relocate dead Gaussians, grow, perturb the means (nothing in the
  *   ms_mcmc_noise                     reference; the CUDA stack's gsplat MCMCStrategy)
+ *   ms_knn                            exact k nearest neighbours of a point cloud, the distances a scene's initial scales
+ *                                     come from (nothing in the reference: it has no training; the CUDA stack's simple-knn)
  *   ms_render_fwd_batch               the same for C cameras: the camera dimension of the reference's
  *                                     kernels (kernels/projection.mojo:32-37) that its wrappers pin to 1
  *
@@ -67,7 +69,7 @@ extern "C" {
 
 #define MS_ABI_VERSION 5   /* 2: ms_render_bwd takes the frame's image (render_colors); 3: ms_render_redo_counts, the band-frame pair, ms_scene_prepare;
                               4: the pose-gradient entry points (ms_pose_scratch_bytes, ms_*_pose); 5: ms_adam_step
-                              (the ms_densify_* and ms_mcmc_* entry points were added under 5: new symbols, nothing existing changed) */
+                              (the ms_densify_*, ms_mcmc_* and ms_knn* entry points were added under 5: new symbols, nothing existing changed) */
 
 typedef enum ms_status {
     MS_OK = 0,
@@ -812,6 +814,32 @@ int ms_mcmc_apply(int64_t N, int64_t n_draws, int64_t n_rows, int grow, void *wo
                   const float *opacities, const float *scales, const float *binom, int logit, double min_opacity, void *stream);
 int ms_mcmc_noise(int64_t N, float *means3d, const float *scales, const float *quats, const float *opacities,
                   const float *noise, int logit, float step, float k, float x0, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Exact k nearest neighbours of every point of a cloud (csrc/knn.hip; the definition: mojosplat_amd/knn.py, knn_torch).
+ * Replaces nothing in the reference (it has no training); the CUDA stack's simple-knn (distCUDA2), which 3DGS sets its
+ * initial scales from.  Enqueues two launches on `stream` and returns: no host synchronisation, no allocation, no atomics,
+ * so the same inputs give the same bits.
+ *
+ * For query i and candidate j != i (self is excluded by ROW, equal points are neighbours at distance 0), in float32 with
+ * every operation rounded on its own:  dx = x_i - x_j, dy, dz likewise, d_ij = ((dx dx) + (dy dy)) + (dz dz).  The candidates
+ * of a query are ordered by (d_ij, j); the first k are its result, in the caller's row order:
+ *   dist2 : f32[N,k]  ascending;   idx : i64[N,k] the neighbours' rows, or NULL (not wanted)
+ *   points: f32[N,3]  finite, |coordinate| <= 1e18 (a square that overflows is the caller's problem)
+ *   order : i32[N]    a permutation of the rows that makes the points spatially coherent (a Morton order), or NULL: as
+ *                     stored.  Blocks of MS_KNN_BLOCK consecutive points of that order are pruned by their bounding boxes, so
+ *                     the order buys speed only: every permutation gives the same, exact result.  An entry outside [0, N) is
+ *                     not dereferenced (the results are then wrong, nothing is accessed out of bounds).
+ *   workspace : ms_knn_workspace_bytes(N, k) bytes, 16-byte aligned (16 N of sorted points, 32 per block of boxes; 0 for
+ *               arguments ms_knn refuses)
+ * k outside [1, MS_KNN_MAX_K], N <= k, a null pointer (points, dist2, workspace), a misaligned pointer (float and int32: 4
+ * bytes, int64: 8, workspace: 16) -> MS_ERR_INVALID_ARG; N >= 2^31 -> MS_ERR_TOO_LARGE; all before any device work.
+ * ------------------------------------------------------------------------------------- */
+#define MS_KNN_BLOCK 64              /* points per bounding box = queries per wave */
+#define MS_KNN_MAX_K 8
+size_t ms_knn_workspace_bytes(int64_t N, int k);
+int ms_knn(int64_t N, const float *points, const int32_t *order, int k, float *dist2, int64_t *idx, void *workspace,
+           void *stream);
 
 #ifdef __cplusplus
 }

@@ -201,6 +201,12 @@ _SIGNATURES["ms_mcmc_apply"] = (c_int, [c_int64, c_int64, c_int64, c_int, c_void
 _SIGNATURES["ms_mcmc_noise"] = (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float,
                                         c_float, c_void_p])
 
+KNN_BLOCK = 64                # MS_KNN_BLOCK: points per bounding box = queries per wave
+KNN_MAX_K = 8
+# exact k nearest neighbours (csrc/knn.hip): N, points, order or None, k, dist2, idx or None, workspace, stream
+_SIGNATURES["ms_knn_workspace_bytes"] = (c_size_t, [c_int64, c_int])
+_SIGNATURES["ms_knn"] = (c_int, [c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p])
+
 # entry points added after ABI v1's first cut; bound when present
 _OPTIONAL = {}
 
