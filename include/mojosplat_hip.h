@@ -34,6 +34,9 @@
  *   ms_mcmc_noise                     reference; the CUDA stack's gsplat MCMCStrategy)
  *   ms_knn                            exact k nearest neighbours of a point cloud, the distances a scene's initial scales
  *                                     come from (nothing in the reference: it has no training; the CUDA stack's simple-knn)
+ *   ms_ply_pack, ms_ply_unpack        the row move between a scene's parameter tensors and the float32 rows of a 3DGS PLY
+ *                                     file (nothing in the reference: it reads and writes no scene; the CUDA stack's
+ *                                     save_ply / load_ply of 3DGS and gsplat's export_splats, composed from torch ops)
  *   ms_render_fwd_batch               the same for C cameras: the camera dimension of the reference's
  *                                     kernels (kernels/projection.mojo:32-37) that its wrappers pin to 1
  *
@@ -69,7 +72,7 @@ extern "C" {
 
 #define MS_ABI_VERSION 5   /* 2: ms_render_bwd takes the frame's image (render_colors); 3: ms_render_redo_counts, the band-frame pair, ms_scene_prepare;
                               4: the pose-gradient entry points (ms_pose_scratch_bytes, ms_*_pose); 5: ms_adam_step
-                              (the ms_densify_*, ms_mcmc_* and ms_knn* entry points were added under 5: new symbols, nothing existing changed) */
+                              (the ms_densify_*, ms_mcmc_*, ms_knn* and ms_ply_* entry points were added under 5: new symbols, nothing existing changed) */
 
 typedef enum ms_status {
     MS_OK = 0,
@@ -840,6 +843,44 @@ int ms_mcmc_noise(int64_t N, float *means3d, const float *scales, const float *q
 size_t ms_knn_workspace_bytes(int64_t N, int k);
 int ms_knn(int64_t N, const float *points, const int32_t *order, int k, float *dist2, int64_t *idx, void *workspace,
            void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Scene files: the row move between the five parameter tensors of a scene and the float32 rows of a 3DGS PLY body
+ * (csrc/sceneio.hip; the file layout and the definition: mojosplat_amd/sceneio.py, pack_ply_rows_torch /
+ * unpack_ply_rows_torch).  Replaces nothing in the reference (it reads and writes no scene); the CUDA stack's save_ply /
+ * load_ply of 3DGS and gsplat's export_splats, which compose the rows from torch ops (permute, reshape, cat).
+ * One launch on `stream` per call: no host synchronisation, no allocation, no workspace, no atomics.  The kernels move BITS:
+ * no value passes through a float operation (NaN payloads and -0.0 survive).
+ *
+ *   tensors : HOST array of MS_PLY_TENSORS device pointers, tensor k f32[N, widths[k]] (the package's order: means3d, scales,
+ *             quats, opacities, features as [N, 3 K])
+ *   widths  : HOST array of their row widths in floats, each in [1, MS_PLY_MAX_COLUMNS], at most MS_PLY_MAX_COLUMNS together
+ *   columns : HOST array of F table entries, F in [1, MS_PLY_MAX_COLUMNS].  An entry ties the file column `column` to float
+ *             `offset` of the row of tensor `tensor`, or to no tensor (tensor = MS_PLY_NONE; offset is then ignored).
+ *   rows    : pack   f32[N, F], out.  Entry by entry rows[n][column] = tensor[n][offset], +0.0 for an entry of no tensor;
+ *                    every column of [0, F) must be named exactly once (every element of rows is written).
+ *             unpack f32[N, S], in, S in [F, MS_PLY_MAX_STRIDE] the file's floats per row.  Entry by entry
+ *                    tensor[n][offset] = rows[n][column], column in [0, S); an entry of no tensor is skipped, as is a column no
+ *                    entry names; every float of every tensor's row must be named exactly once (every element of every
+ *                    tensor is written).
+ * A workgroup moves MS_PLY_ROWS consecutive rows through LDS; 16-byte accesses on every array whose base is 16-byte aligned,
+ * dwords otherwise; every element index is 64-bit.  N = 0 is a no-op.  N < 0, a null or misaligned (4 bytes) pointer, F, S or a
+ * width out of range, a table entry whose tensor, offset or column is out of range, a column (pack) or a tensor float
+ * (unpack) named twice or (unpack) not at all -> MS_ERR_INVALID_ARG; more than (2^31 - 1) MS_PLY_ROWS rows ->
+ * MS_ERR_TOO_LARGE; all before any device work.
+ * ------------------------------------------------------------------------------------- */
+#define MS_PLY_ROWS 64               /* rows per workgroup */
+#define MS_PLY_TENSORS 5
+#define MS_PLY_MAX_COLUMNS 128       /* table entries, and floats of the five tensors' rows together */
+#define MS_PLY_MAX_STRIDE 192        /* floats per row of the rows ms_ply_unpack reads (64 rows of them are staged in LDS) */
+#define MS_PLY_NONE (-1)
+typedef struct ms_ply_column {
+    int32_t tensor, offset, column;
+} ms_ply_column;
+int ms_ply_pack(int64_t N, int F, const float *const *tensors, const int32_t *widths, const ms_ply_column *columns, float *rows,
+                void *stream);
+int ms_ply_unpack(int64_t N, int F, int S, const float *rows, float *const *tensors, const int32_t *widths,
+                  const ms_ply_column *columns, void *stream);
 
 #ifdef __cplusplus
 }

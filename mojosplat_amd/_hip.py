@@ -207,6 +207,23 @@ KNN_MAX_K = 8
 _SIGNATURES["ms_knn_workspace_bytes"] = (c_size_t, [c_int64, c_int])
 _SIGNATURES["ms_knn"] = (c_int, [c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p])
 
+
+class PlyColumn(ctypes.Structure):
+    """ms_ply_column (include/mojosplat_hip.h): file column <-> (tensor, float offset in its row), or no tensor."""
+    _fields_ = [("tensor", c_int), ("offset", c_int), ("column", c_int)]
+
+
+PLY_ROWS = 64                 # MS_PLY_ROWS: rows per workgroup
+PLY_TENSORS = 5
+PLY_MAX_COLUMNS = 128
+PLY_MAX_STRIDE = 192
+PLY_NONE = -1
+# scene files (csrc/sceneio.hip): N, F, [S, rows,] tensors (host array of 5), widths (host), the table (host), [rows,] stream
+_SIGNATURES["ms_ply_pack"] = (c_int, [c_int64, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), ctypes.POINTER(PlyColumn),
+                                      c_void_p, c_void_p])
+_SIGNATURES["ms_ply_unpack"] = (c_int, [c_int64, c_int, c_int, c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_int),
+                                        ctypes.POINTER(PlyColumn), c_void_p])
+
 # entry points added after ABI v1's first cut; bound when present
 _OPTIONAL = {}
 
