@@ -60,7 +60,18 @@ def clear_scenes():
         _last = None
 
 
-_last = None   # (the five tensor OBJECTS of the previous call, their versions, the struct): a render loop's fast path
+_last = None   # (the five tensor OBJECTS of the previous call, what _sig saw of them, the struct, its key): a render loop's fast path
+
+
+def _sig(a, b, c, d, e):
+    """What a cached ms_scene depends on, of the very same five tensor objects: where they point, their versions, extents,
+    strides and types (_tkey's fields) -- ``t.data = other`` keeps the object AND its version counter and changes the rest
+    (``t.data = t.data[:k]``: the extent alone; a transposed alias of the same memory: the strides alone).  One flat tuple
+    of attribute reads: this runs on every band frame."""
+    return (a.data_ptr(), b.data_ptr(), c.data_ptr(), d.data_ptr(), e.data_ptr(),
+            a._version, b._version, c._version, d._version, e._version,
+            a.shape, b.shape, c.shape, d.shape, e.shape, a.stride(), b.stride(), c.stride(), d.stride(), e.stride(),
+            a.dtype, b.dtype, c.dtype, d.dtype, e.dtype)
 
 
 def scene_struct(means3d, scales, quats, opacities, colors):
@@ -68,14 +79,13 @@ def scene_struct(means3d, scales, quats, opacities, colors):
     global _last
     with _fused._frame_lock:
         L = _last
-        # the very same tensor objects, unmodified since (a view such as means3d[:k] is a NEW object each time: slow path)
+        # the very same tensor objects, unmodified since (a view such as means3d[:k] is a NEW object each time: slow path) and
+        # still on the same storage
         if (L is not None and L[0] is means3d and L[1] is scales and L[2] is quats and L[3] is opacities and L[4] is colors and
-                L[5] == (means3d._version, scales._version, quats._version, opacities._version, colors._version) and
-                L[6].N == means3d.shape[0] and L[7] in _scenes):
+                L[5] == _sig(means3d, scales, quats, opacities, colors) and L[7] in _scenes):
             return L[6]
         S = _scene_struct(means3d, scales, quats, opacities, colors)
-        _last = (means3d, scales, quats, opacities, colors,
-                 (means3d._version, scales._version, quats._version, opacities._version, colors._version), S, S._key)
+        _last = (means3d, scales, quats, opacities, colors, _sig(means3d, scales, quats, opacities, colors), S, S._key)
         return S
 
 

@@ -86,10 +86,10 @@ def release_scratch():
         for dev in devs:
             torch.cuda.synchronize(dev)
         _state.clear()
-        # (round 6, advisor: the scene caches pin whole scenes -- marshalled copies, prepared bounds -- on the device)
-        from . import _band, scene_order
+        # (round 6, advisor: the scene cache pins whole scenes -- marshalled copies -- on the device.  The prepared-scene registry
+        # stays: it holds weak references only, and a live PreparedScene has no other way to its bounds)
+        from . import _band
         _band.clear_scenes()
-        scene_order.clear_registry()
 
 
 def _dev_state(dev, lane=0):

@@ -84,6 +84,7 @@ class _ProjectHip(torch.autograd.Function):
                 _hip.check(L.ms_densify_stats_update(N, cam.W, cam.H, _hip.ptr(radii), _hip.ptr(v_means2d), _hip.ptr(st.grad2d),
                                                      _hip.ptr(st.count), _hip.ptr(st.max_radii), _hip.stream(dev)),
                            "ms_densify_stats_update")
+                _hip.bump(st.grad2d, st.count, st.max_radii)   # (as densify.update_torch's three index assignments)
         return v_means3d, v_scales, v_quats, None, None, None, _pose_grad(v_vm, ctx.vm_meta) if pose else None
 
 
@@ -255,6 +256,7 @@ class _RenderFusedHip(torch.autograd.Function):
                         cam.W, cam.H, EPS2D, _hip.ptr(rows), _hip.ptr(v_means3d), _hip.ptr(v_scales), _hip.ptr(v_quats), _hip.ptr(v_opac),
                         _hip.ptr(v_colors), cam.near, cam.far, _hip.ptr(dst.grad2d), _hip.ptr(dst.count), _hip.ptr(dst.max_radii),
                         *pose_args, _hip.stream(dev)), "ms_render_bwd_finish_densify")
+                    _hip.bump(dst.grad2d, dst.count, dst.max_radii)   # (as densify.update_torch's three index assignments)
                 if bev:
                     bev[2].record()
                 if fronts:

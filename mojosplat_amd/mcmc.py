@@ -273,12 +273,6 @@ def _check_draws(draws, sampled, n, dev, backend):
             raise ValueError(f"backend='hip': {name} must be contiguous")
 
 
-def _bump(t):
-    """An in-place torch op on an empty view: the tensor's version counter moves (the kernels write through raw pointers,
-    and the sharded path's scene cache goes by ``_version``), nothing is launched."""
-    t.detach()[:0].zero_()
-
-
 # ---------------------------------------------------------------------------------------------------------- backend="hip"
 def _apply_hip(L, _hip, tensors, moments, N, n_draws, n_rows, grow, ws, sampled, targets, logit, min_opacity, dev, stream):
     """ms_mcmc_apply over every tensor of ``tensors`` {name: (n_rows, ...)} and ``moments`` {name: [exp_avg, exp_avg_sq]}."""
@@ -330,8 +324,8 @@ def _relocate_dead_hip(params, opt, N, dev, min_opacity, opacity_space, draws, s
                                         _hip.ptr(draws), _hip.ptr(sampled), _hip.ptr(ws), ws.numel(), _hip.ptr(out_s),
                                         _hip.ptr(out_t), _hip.ptr(n), stream), "ms_mcmc_sample")
             _apply_hip(L, _hip, params, moments, N, N, N, 0, ws, out_s, out_t, logit, min_opacity, dev, stream)
-        for p in params.values():
-            _bump(p)
+        # (written through raw pointers: the version counters move where relocate_dead_torch's index assignments move them)
+        _hip.bump(*params.values(), *[m for ms_ in moments.values() for m in ms_])
     return McmcResult(params, out_s, out_t, n)
 
 
@@ -446,7 +440,7 @@ def inject_noise(params, lr, *, noise_lr=5e5, opacity_space="logit", k=100.0, x0
         _hip.check(L.ms_mcmc_noise(N, _hip.ptr(params["means3d"]), _hip.ptr(params["scales"]), _hip.ptr(params["quats"]),
                                    _hip.ptr(params["opacities"]), _hip.ptr(noise), int(opacity_space == "logit"),
                                    lr * noise_lr, k, x0, _hip.stream(dev)), "ms_mcmc_noise")
-    _bump(params["means3d"])
+    _hip.bump(params["means3d"])                        # (the only tensor the kernel writes, as inject_noise_torch's add_)
 
 
 __all__ = ["relocate_dead", "grow", "inject_noise", "McmcResult", "relocate_dead_torch", "grow_torch", "inject_noise_torch",

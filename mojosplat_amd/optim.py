@@ -205,6 +205,9 @@ class GaussianAdam(torch.optim.Optimizer):
                     rec.lr, rec.beta1, rec.beta2, rec.eps = lr, b1, b2, eps
                     rec.bias_correction1, rec.bias_correction2_sqrt = 1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t)
                 _hip.check(L.ms_adam_step(len(chunk), table, vis_ptr, vis_rows, stream), "ms_adam_step")
+        # the kernel wrote through raw pointers: the version counters move as adam_update_torch's three copy_ move them (masked
+        # or not, and for a tensor without elements too), so the scene caches and autograd's saved-tensor check see the step
+        _hip.bump(*[t for p, _, st, *_ in work for t in (p, st["exp_avg"], st["exp_avg_sq"])])
 
     # ------------------------------------------------------------------ densification
     def _rows(self, keep, n_old, device):

@@ -55,7 +55,8 @@ class PreparedScene:
         return (self.means3d, self.scales, self.quats, self.opacities, self.features)
 
 
-# id(means3d) -> (weakref to means3d, means version, scales weakref, scales version, block bounds, block size).  Round 6
+# id(means3d) -> (weakref to means3d, means version, scales weakref, scales version, block bounds, block size, the two data
+# pointers -- ``t.data = other`` keeps object and version and moves the pointer).  Round 6
 # (advisor): the entry holds NO strong reference to the scene's arrays -- a PreparedScene the caller has dropped frees its
 # Gaussians, and a finalizer on the means takes the entry (and the bounds buffer it keeps) out.
 _registry = {}
@@ -63,6 +64,9 @@ _registry_lock = __import__("threading").Lock()
 
 
 def clear_registry():
+    """Forget every prepared scene's bounds (they render as unprepared scenes from then on): the explicit call for arrays
+    that were rewritten behind torch's back.  Nothing else clears the registry -- its entries hold weak references and go
+    with their means."""
     with _registry_lock:
         _registry.clear()
 
@@ -77,9 +81,10 @@ def prepare_scene(means3d, scales, quats, opacities, features, block_size: int =
     spatially coherent for the bounds to be worth anything -- any order stays CORRECT) and compute the bounds of every
     block of `block_size` of them (ms_scene_prepare).  Once per scene: ~2 ms at 5 M Gaussians.  The scales are the
     LOG-scales render_gaussians takes.  The bounds describe the arrays as they are now: call again after the means or
-    scales change (an in-place update is noticed through the tensors' version counters and the bounds are dropped)."""
+    scales change (an in-place update is noticed through the tensors' version counters, a storage swap through their data
+    pointers, and the bounds are dropped; a write that moves neither -- through a numpy / DLPack alias, by a foreign kernel
+    -- is the caller's to announce: INTEGRATION.md, "In-place writers")."""
     import ctypes
-    import weakref
     from . import _hip
     _hip.require_cuda(means3d, scales, quats, opacities, features, what="gaussian tensor")
     perm = None
@@ -98,10 +103,16 @@ def prepare_scene(means3d, scales, quats, opacities, features, block_size: int =
     # the view below keeps all of it alive and starts where the buffer does)
     nb = -(-N // block_size) if N > 0 else 0
     ps = PreparedScene(m, sc, quats, opacities, features, perm, bounds[:max(nb, 1) * 8].view(-1, 8), block_size)
-    with _registry_lock:
-        _registry[id(m)] = (weakref.ref(m), m._version, weakref.ref(sc), sc._version, ps.block_bounds, block_size)
-    weakref.finalize(m, _forget, id(m))
+    _register(m, sc, ps.block_bounds, block_size)
     return ps
+
+
+def _register(m, sc, bounds, block_size):
+    """The registry entry of a prepared scene's means and scales as they are now; it goes when the means do."""
+    import weakref
+    with _registry_lock:
+        _registry[id(m)] = (weakref.ref(m), m._version, weakref.ref(sc), sc._version, bounds, block_size, m.data_ptr(), sc.data_ptr())
+    weakref.finalize(m, _forget, id(m))
 
 
 def prepared_bounds(means3d, scales):
@@ -110,7 +121,11 @@ def prepared_bounds(means3d, scales):
         rec = _registry.get(id(means3d))
     if rec is None:
         return None
-    m_ref, m_ver, s_ref, s_ver, bounds, block_size = rec
+    m_ref, m_ver, s_ref, s_ver, bounds, block_size = rec[:6]
     if m_ref() is not means3d or s_ref() is not scales or means3d._version != m_ver or scales._version != s_ver:
+        return None
+    # (a storage swap: same objects, same versions.  An entry written without the two pointers -- the six fields of earlier
+    # versions, by a caller's own code -- is checked as far as it goes)
+    if len(rec) >= 8 and (means3d.data_ptr() != rec[6] or scales.data_ptr() != rec[7]):
         return None
     return bounds, block_size

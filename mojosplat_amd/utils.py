@@ -45,10 +45,10 @@ class Camera:
         the (1,9) intrinsics tensor the reference rebuilds per call at projection.py:446)."""
         vm = self.view_matrix
         cached = getattr(self, "_vm_cache", None)
-        if cached is not None and cached[0] is vm and cached[1] == vm._version:
+        if cached is not None and cached[0] is vm and cached[1] == _vm_key(vm):
             return cached[2]
         flat = vm.detach().to(torch.float32).contiguous().view(16)
-        self._vm_cache = (vm, vm._version, flat)
+        self._vm_cache = (vm, _vm_key(vm), flat)
         return flat
 
     def _campos(self):
@@ -56,12 +56,18 @@ class Camera:
         projection uses: -R^T T.  Cached (one D2H read per camera, not per frame)."""
         vm = self.view_matrix
         cached = getattr(self, "_cp_cache", None)
-        if cached is not None and cached[0] is vm and cached[1] == vm._version:
+        if cached is not None and cached[0] is vm and cached[1] == _vm_key(vm):
             return cached[2]
         m = vm.detach().to(torch.float64).cpu()
         pos = tuple(float(v) for v in (-(m[:3, :3].T @ m[:3, 3])).tolist())
-        self._cp_cache = (vm, vm._version, pos)
+        self._cp_cache = (vm, _vm_key(vm), pos)
         return pos
+
+
+def _vm_key(vm):
+    """What the two caches above hold of a view matrix OBJECT: its version counter (in-place updates) and where and how
+    it is stored -- ``vm.data = other`` keeps the object and its version."""
+    return (vm._version, vm.data_ptr(), vm.shape, vm.stride(), vm.dtype)
 
 
 def look_at(eye: torch.Tensor, target: torch.Tensor, up: torch.Tensor) -> torch.Tensor:

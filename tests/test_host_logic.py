@@ -373,12 +373,27 @@ def test_scene_cache_key_tells_views_apart_and_registry_holds_no_scene():
     # the registry: an entry built by hand the way prepare_scene builds it
     sc = torch.zeros(100, 3)
     bounds = torch.zeros(1, 8)
+    # (an entry of the six fields earlier versions wrote, without the data pointers, still answers)
     with scene_order._registry_lock:
         scene_order._registry[id(m)] = (weakref.ref(m), m._version, weakref.ref(sc), sc._version, bounds, 256)
-    weakref.finalize(m, scene_order._forget, id(m))
+    assert scene_order.prepared_bounds(m, sc)[1] == 256
+    scene_order._register(m, sc, bounds, 256)
     assert scene_order.prepared_bounds(m, sc) == (bounds, 256) or scene_order.prepared_bounds(m, sc)[1] == 256
     assert scene_order.prepared_bounds(m[:10], sc) is None      # (a view is another object)
     key = id(m)
+    # a storage swap keeps the object and its version counter: the bounds describe the old storage's values
+    for swap in ("means.data", "scales.data", "means.set_", "scales.set_"):
+        t = m if swap.startswith("means") else sc
+        old_storage, version = t.detach()[:], t._version        # (the old storage stays referenced)
+        if swap.endswith(".data"):
+            t.data = torch.ones(100, 3)
+        else:
+            t.set_(torch.ones(100, 3))
+        # (``.data =`` keeps the version counter; ``set_`` counts as an in-place op in torch and moves it)
+        assert (t._version == version or swap.endswith("set_")) and t.data_ptr() != old_storage.data_ptr()
+        assert scene_order.prepared_bounds(m, sc) is None, swap
+        scene_order._register(m, sc, bounds, 256)                # (prepare_scene again: the remedy)
+        assert scene_order.prepared_bounds(m, sc)[1] == 256
     sc.add_(1.0)
     assert scene_order.prepared_bounds(m, sc) is None           # scales changed in place: bounds void
     del m
@@ -400,6 +415,25 @@ def test_band_scene_cache_on_cpu_tensors_prefix_views_and_the_fast_path():
     S_full = _band.scene_struct(*g)
     assert S_full.N == n and S_full.CDIM == 3
     assert _band.scene_struct(*g) is S_full                      # fast path: same objects, same versions
+    # a storage swap keeps the tensor OBJECT and its version counter: a new struct on the new storage, none left on the old
+    # (which stays referenced here; on a GPU the allocator would hand it out again)
+    fields = ("means3d", "scales")
+    for k, swap in ((0, "data"), (1, "set_")):
+        S_before, old_storage, version = _band.scene_struct(*g), g[k].detach()[:], g[k]._version
+        assert getattr(S_before, fields[k]) == old_storage.data_ptr()
+        if swap == "data":
+            g[k].data = torch.randn(n, 3)
+        else:
+            g[k].set_(torch.randn(n, 3))
+        # (``.data =`` keeps the version counter; ``set_`` counts as an in-place op in torch and moves it)
+        assert (g[k]._version == version or swap == "set_") and g[k].data_ptr() != old_storage.data_ptr()
+        S_swapped = _band.scene_struct(*g)
+        assert S_swapped is not S_before and S_swapped.N == n, swap
+        assert getattr(S_swapped, fields[k]) == g[k].data_ptr(), swap
+        assert all(getattr(v[0], fields[k]) != old_storage.data_ptr() for v in _band._scenes.values()), swap
+        assert _band.scene_struct(*g) is S_swapped               # ... and the fast path again
+    assert all(v[0] is not S_full for v in _band._scenes.values()) and len(_band._scenes) == 1
+    S_full = _band.scene_struct(*g)                              # (the scene as it is now, for what follows)
     gk = tuple(t[:40] for t in g)
     S_k = _band.scene_struct(*gk)
     assert S_k is not S_full and S_k.N == 40
@@ -415,3 +449,105 @@ def test_band_scene_cache_on_cpu_tensors_prefix_views_and_the_fast_path():
     assert S3.N == n and S3.means3d != gd[0].data_ptr() and any(t.dtype == torch.float32 and t.data_ptr() == S3.means3d for t in S3._keep)
     _band.clear_scenes()
     assert not _band._scenes and _band._last is None
+
+
+def _camera_with(vm):
+    from mojosplat_amd.utils import Camera
+    return Camera(R=vm[:3, :3], T=vm[:3, 3], H=48, W=64, fx=50.0, fy=55.0, cx=31.0, cy=25.0, view_matrix=vm)
+
+
+def _pose(seed, dtype):
+    """A rigid world->camera matrix (a rotation from a QR factorisation, a translation of a few units), float64 -> dtype."""
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    q, _ = torch.linalg.qr(torch.randn(3, 3, generator=g, dtype=torch.float64))
+    vm = torch.eye(4, dtype=torch.float64)
+    vm[:3, :3] = q
+    vm[:3, 3] = torch.randn(3, generator=g, dtype=torch.float64) * 3.0 + 1.0
+    return vm.to(dtype)
+
+
+@pytest.mark.parametrize("layout", ["float32", "float64", "noncontiguous"])
+@pytest.mark.parametrize("update", ["inplace", "data", "set_"])
+def test_camera_caches_follow_in_place_updates_and_storage_swaps(layout, update):
+    """Camera._viewmat_f32 (the matrix the projection reads) and Camera._campos (the centre the SH colours are evaluated
+    from) are cached per view-matrix OBJECT: untouched, both return the cached object; after an in-place torch op, after
+    ``vm.data = other`` (which keeps object and version counter) and after ``vm.set_(other)`` both describe the CURRENT
+    matrix -- the float32 cast exactly, the centre -R^T T formed in float64 to 1e-12 of its largest component.  One frame is
+    never made from two cameras."""
+    import torch
+
+    def make(seed):
+        vm = _pose(seed, torch.float64 if layout == "float64" else torch.float32)
+        return vm.t().contiguous().t() if layout == "noncontiguous" else vm
+
+    def check(cam, what):
+        vm = cam.view_matrix
+        m = vm.detach().double().numpy()
+        want = -(m[:3, :3].T @ m[:3, 3])
+        got = cam._campos()
+        assert isinstance(got, tuple) and len(got) == 3 and all(isinstance(v, float) for v in got)
+        err = max(abs(a - b) for a, b in zip(got, want)) / max(abs(want).max(), 1e-300)
+        assert err <= 1e-12, (what, err, got, want)
+        flat = cam._viewmat_f32()
+        assert flat.dtype == torch.float32 and flat.shape == (16,) and flat.is_contiguous()
+        assert torch.equal(flat.view(4, 4), vm.detach().to(torch.float32)), what
+        assert cam._campos() is got and cam._viewmat_f32() is flat, f"{what}: untouched, the caches answer"
+        return got, flat
+
+    vm = make(1)
+    assert vm.is_contiguous() == (layout != "noncontiguous")
+    cam = _camera_with(vm)
+    c0, f0 = check(cam, "fresh")
+    other = make(2)
+    version = vm._version
+    if update == "inplace":
+        with torch.no_grad():
+            vm[:3, 3] += torch.tensor([0.5, -1.0, 2.0], dtype=vm.dtype)
+            vm[:3, :3] = other[:3, :3]
+        assert vm._version > version
+    else:
+        old_storage = vm.detach()[:]                              # (stays referenced: nothing reads freed memory)
+        if update == "data":
+            vm.data = other
+        else:
+            vm.set_(other)
+        # (``.data =`` keeps the version counter; ``set_`` counts as an in-place op in torch and moves it)
+        assert (vm._version == version or update == "set_") and cam.view_matrix is vm and vm.data_ptr() != old_storage.data_ptr()
+    c1, f1 = check(cam, update)
+    assert max(abs(a - b) for a, b in zip(c0, c1)) > 0.1, "the update moved the camera: a stale cache cannot pass"
+    # ... and once more, so that the entry made after an update is itself checked against the next one
+    with torch.no_grad():
+        vm.mul_(1.0).add_(torch.zeros_like(vm))
+        vm[0, 3] += 1.0
+    check(cam, update + ", then in place")
+
+
+@pytest.mark.parametrize("how", ["setter", "inplace_op"])
+def test_bump_moves_the_version_counter_of_any_tensor_and_nothing_else(how, monkeypatch):
+    """_hip.bump, what every in-place HIP writer calls on the tensors it wrote through raw pointers: the version counter
+    moves (autograd's saved-tensor check and the scene caches see it), the values, the storage and ``requires_grad`` stay --
+    for a leaf that requires grad (outside no_grad too), a 0-dim parameter, an empty one, a strided view, an integer tensor;
+    a view's bump is its base's."""
+    import torch
+    if how == "inplace_op":                      # (a torch without the version-counter setter: an in-place op on an empty view)
+        monkeypatch.setattr(_hip, "_set_versions", None)
+    base = torch.arange(24.0).reshape(4, 6)
+    cases = {"leaf": torch.randn(5, 3).requires_grad_(), "zero_dim": torch.tensor(2.5, requires_grad=True),
+             "empty": torch.zeros(0, 3), "strided": base[:, ::2], "int": torch.arange(7)}
+    for name, t in cases.items():
+        before, version, ptr = t.detach().clone(), t._version, t.data_ptr()
+        _hip.bump(t)
+        assert t._version > version, name
+        assert torch.equal(t.detach(), before) and t.data_ptr() == ptr and t.requires_grad == (name in ("leaf", "zero_dim")), name
+    assert base._version > 0, "a view shares its base's counter"
+    a, b = torch.zeros(3), torch.zeros(2)
+    _hip.bump(a, b)
+    assert a._version == 1 and b._version == 1
+    # what the counter is for: a graph that saved the tensor before the write refuses a backward after it
+    p = torch.randn(4, requires_grad=True)
+    y = (p * p).sum()
+    _hip.bump(p)
+    with pytest.raises(RuntimeError, match="inplace"):
+        y.backward()
+
