@@ -2448,13 +2448,12 @@ int ms::far_regen(const ms::LazyLists &lazy, int tw, int n_tiles, int64_t cap, v
     Candidates cand{nullptr, nullptr, 0, 0};
     if (I.band_cull) {   // the band's candidate list, where the frame's count launch left it
         Plan p;
-        MS_REQUIRE(I.isect_workspace && make_plan(I.N, tw, th_, I.row_begin, I.row_end, p), MS_ERR_INVALID_ARG, "far_regen: a pre-culled band without its workspace");
+        MS_REQUIRE(I.isect_workspace && make_plan(I.g.N, tw, th_, I.row_begin, I.row_end, p), MS_ERR_INVALID_ARG, "far_regen: a pre-culled band without its workspace");
         const char *ws = (const char *)I.isect_workspace;
         cand = Candidates{(const int32_t *)(ws + p.off_cand), (const int32_t *)(ws + p.off_cand_count), p.G, p.chunk};
     }
-    const RegenProject R{I.means3d, I.scales, I.quats, I.opacities, I.viewmat, I.colors, I.color_f16,
-                         ms::make_proj_params(I.fx, I.fy, I.cx, I.cy, I.W, I.H, I.eps2d, I.near_plane, I.far_plane, 0.0f, I.scales_are_log,
-                                              I.opacities != nullptr),
+    const RegenProject R{I.g.means3d, I.g.scales, I.g.quats, I.g.opacities, I.v.viewmat, I.g.colors, I.g.color_dtype == MS_COLOR_F16 ? 1 : 0,
+                         ms::make_proj_params(I.v, 0.0f, I.g.scales_are_log, I.g.opacities != nullptr),
                          (float4 *)I.records,
                          // (the band's rows: the count kernel clamped every box to them, and the reach masks' bits count from there)
                          Grid{I.tile_size, tw, th_, I.row_begin, I.row_end, 0, 0, 0}, cand};
@@ -2620,38 +2619,35 @@ extern "C" int ms_project_isect_count(int64_t N, const float *means3d, const flo
                                       int32_t *radii, void *workspace, size_t workspace_bytes,
                                       int32_t *tile_ranges, int64_t *isect_info, int64_t *isect_info_mirror,
                                       void *stream_) {
-    return ms::project_isect_count(N, means3d, scales, scales_are_log, quats, opacities, viewmat, fx, fy, cx, cy, W, H,
-                                   eps2d, near_plane, far_plane, radius_clip, tile_size, row_begin, row_end, tight & 63,
-                                   means2d, conics, depths, radii, workspace, workspace_bytes, tile_ranges, isect_info,
-                                   isect_info_mirror, nullptr, 0, nullptr, stream_, 0u);
+    const ms::Gaussians g{N, means3d, scales, scales_are_log, quats, opacities, nullptr, 0, 0};
+    const ms::View v{viewmat, fx, fy, cx, cy, W, H, eps2d, near_plane, far_plane};
+    return ms::project_isect_count(g, v, radius_clip, tile_size, row_begin, row_end, tight & 63, means2d, conics, depths, radii,
+                                   workspace, workspace_bytes, tile_ranges, isect_info, isect_info_mirror, nullptr, stream_, 0u);
 }
 
-int ms::project_isect_count(int64_t N, const float *means3d, const float *scales, int scales_are_log,
-                            const float *quats, const float *opacities, const float *viewmat,
-                            float fx, float fy, float cx, float cy, int W, int H, float eps2d,
-                            float near_plane, float far_plane, float radius_clip, int tile_size,
-                            int row_begin, int row_end, int tight, float *means2d, float *conics,
-                            float *depths,
-                            int32_t *radii, void *workspace, size_t workspace_bytes,
-                            int32_t *tile_ranges, int64_t *isect_info, int64_t *isect_info_mirror,
-                            const void *colors3, int color_dtype, void *raster_records, void *stream_, uint32_t cut_stamp,
+int ms::project_isect_count(const ms::Gaussians &gs, const ms::View &v, float radius_clip, int tile_size, int row_begin,
+                            int row_end, int tight, float *means2d, float *conics, float *depths, int32_t *radii,
+                            void *workspace, size_t workspace_bytes, int32_t *tile_ranges, int64_t *isect_info,
+                            int64_t *isect_info_mirror, void *raster_records, void *stream_, uint32_t cut_stamp,
                             const float *block_bounds, int block_size) {
+    const int64_t N = gs.N;
     hipStream_t stream = (hipStream_t)stream_;
-    if (!opacities || !colors3) raster_records = nullptr;
+    const void *colors3 = raster_records ? gs.colors : nullptr;   // (read for the records alone)
+    if (!gs.opacities || !colors3) raster_records = nullptr;
     int block_shift = 0;
     if (block_bounds) {
         MS_REQUIRE(block_size >= 64 && (block_size & (block_size - 1)) == 0, MS_ERR_INVALID_ARG,
                    "project_isect_count: a prepared scene's block size must be a power of two >= 64 (got %d)", block_size);
         while ((1 << block_shift) < block_size) ++block_shift;
     }
-    MS_REQUIRE(N >= 0 && W > 0 && H > 0 && tile_size > 0 && fx != 0.f && fy != 0.f, MS_ERR_INVALID_ARG,
+    MS_REQUIRE(N >= 0 && v.W > 0 && v.H > 0 && tile_size > 0 && v.fx != 0.f && v.fy != 0.f, MS_ERR_INVALID_ARG,
                "project_isect_count: bad sizes / camera");
-    const int tile_w = (W + tile_size - 1) / tile_size, tile_h = (H + tile_size - 1) / tile_size;
+    const int tile_w = (v.W + tile_size - 1) / tile_size, tile_h = (v.H + tile_size - 1) / tile_size;
     if (int rc = check_grid(tile_size, tile_w, tile_h, row_begin, row_end)) return rc;
     MS_REQUIRE(workspace && tile_ranges && isect_info &&
-                   (N == 0 || (means3d && scales && quats && viewmat && means2d && conics && depths && radii)),
+                   (N == 0 || (gs.means3d && gs.scales && gs.quats && v.viewmat && means2d && conics && depths && radii)),
                MS_ERR_INVALID_ARG, "project_isect_count: null pointer");
-    MS_REQUIRE(((uintptr_t)quats & 15) == 0 && ((uintptr_t)means2d & 7) == 0 && ((uintptr_t)radii & 7) == 0 &&
+    MS_REQUIRE(((uintptr_t)gs.quats & 15) == 0 && ((uintptr_t)means2d & 7) == 0 && ((uintptr_t)radii & 7) == 0 &&
                    ((uintptr_t)tile_ranges & 7) == 0,
                MS_ERR_INVALID_ARG, "project_isect_count: quats 16-byte, means2d/radii/tile_ranges 8-byte aligned");
     Plan p;
@@ -2668,19 +2664,18 @@ int ms::project_isect_count(int64_t N, const float *means3d, const float *scales
     uint32_t *on_grid = (uint32_t *)(ws + p.off_on_grid);
     // block masks (bit 2): entries carry the 2x2 half-tile blocks they reach; bits 3 / 4: the half-tile
     // grid has an odd number of columns / rows (2 tile_w - 1, 2 tile_h - 1)
-    const bool pack = (tight & 4) && (tight & 1) && opacities && (tile_size & 1) == 0 && N < (1ll << 28);
+    const bool pack = (tight & 4) && (tight & 1) && gs.opacities && (tile_size & 1) == 0 && N < (1ll << 28);
     const Grid g{tile_size, tile_w, tile_h, row_begin, row_end, pack ? 1 : 0, 2 * tile_w - ((tight >> 3) & 1),
                  2 * tile_h - ((tight >> 4) & 1)};
-    unsigned long long *masks = ((tight & 1) && opacities) ? (unsigned long long *)(ws + p.off_mask) : nullptr;
-    const ms::ProjParams P = ms::make_proj_params(fx, fy, cx, cy, W, H, eps2d, near_plane, far_plane, radius_clip,
-                                                  scales_are_log, opacities != nullptr);
+    unsigned long long *masks = ((tight & 1) && gs.opacities) ? (unsigned long long *)(ws + p.off_mask) : nullptr;
+    const ms::ProjParams P = ms::make_proj_params(v, radius_clip, gs.scales_are_log, gs.opacities != nullptr);
     // bit 5 of `tight`: the band is a rank's share of a frame -- pre-cull the Gaussians that cannot reach it
     Candidates cand{nullptr, nullptr, 0, 0};
     if ((tight & kBandCull) && N >= (1ll << 28)) tight &= ~kBandCull;   // (the candidates' gather indexes with 32-bit byte offsets)
     if ((tight & kBandCull) && N > 0) {
         int32_t *seg_count = (int32_t *)(ws + p.off_cand_count);
         hipLaunchKernelGGL(block_bounds ? k_band_precull<true> : k_band_precull<false>, dim3(p.G), dim3(kHistThreads), 0, stream, N,
-                           means3d, scales, viewmat, P, (float)(row_begin * tile_size) - 1.0f, (float)(row_end * tile_size) + 1.0f,
+                           gs.means3d, gs.scales, v.viewmat, P, (float)(row_begin * tile_size) - 1.0f, (float)(row_end * tile_size) + 1.0f,
                            p.chunk, (int32_t *)(ws + p.off_cand), seg_count, block_bounds, block_shift);
         MS_LAUNCH_CHECK();
         cand = Candidates{(const int32_t *)(ws + p.off_cand), seg_count, p.G, p.chunk};
@@ -2710,9 +2705,9 @@ int ms::project_isect_count(int64_t N, const float *means3d, const float *scales
         lds = (size_t)big_q_off + (size_t)big_q_cap * 32;
         if (lds > 48 * 1024)
             if (int rc = allow_big_lds(kernel)) return rc;
-        hipLaunchKernelGGL(kernel, dim3(p.G), dim3(kHistThreads), lds, stream, N, means3d, scales,
-                           quats, opacities, viewmat, P, g, p.chunk, means2d, conics, depths, radii, hist, on_grid, masks,
-                           colors3, color_dtype == MS_COLOR_F16 ? 1 : 0, (float4 *)raster_records, cand,
+        hipLaunchKernelGGL(kernel, dim3(p.G), dim3(kHistThreads), lds, stream, N, gs.means3d, gs.scales,
+                           gs.quats, gs.opacities, v.viewmat, P, g, p.chunk, means2d, conics, depths, radii, hist, on_grid, masks,
+                           colors3, gs.color_dtype == MS_COLOR_F16 ? 1 : 0, (float4 *)raster_records, cand,
                            (LeanRec *)(ws + p.off_lean), (uint32_t *)(ws + p.off_depth_wg),
                            cut ? (const uint32_t *)(ws + p.off_tau) + (size_t)((tight >> 9) & 1) * p.T : nullptr, (uint32_t *)(ws + p.off_wg_far),
                            (uint32_t *)(ws + p.off_has_far), cut_stamp, (LeanRec *)(ws + p.off_near), (tight & ms::kTightKeepArrays) ? 1 : 0, p.near_cap,

@@ -76,15 +76,78 @@ __device__ __forceinline__ RasterRecord make_raster_record(float mx, float my, f
 }
 #endif
 
-// binning.hip: ms_project_isect_count that also writes the rasteriser's records (raster_records: N x 48 B,
-// or null; colors3: the frame's colours, 3 channels, f32 or f16)
-int project_isect_count(int64_t N, const float *means3d, const float *scales, int scales_are_log,
-                        const float *quats, const float *opacities, const float *viewmat, float fx, float fy,
-                        float cx, float cy, int W, int H, float eps2d, float near_plane, float far_plane,
-                        float radius_clip, int tile_size, int row_begin, int row_end, int tight, float *means2d,
-                        float *conics, float *depths, int32_t *radii, void *workspace, size_t workspace_bytes,
-                        int32_t *tile_ranges, int64_t *isect_info, int64_t *isect_info_mirror,
-                        const void *colors3, int color_dtype, void *raster_records, void *stream, uint32_t cut_stamp = 0,
+// What every entry point is handed, packed ONCE at the C ABI boundary (each extern "C" function fills them at its top, in
+// the header's own argument order) and passed down by const reference: below that line no function takes a scalar scene or
+// camera parameter, so two floats of a camera cannot change places on the way to a kernel.
+struct Gaussians {
+    int64_t N;
+    const float *means3d, *scales;
+    int scales_are_log;
+    const float *quats, *opacities;
+    const void *colors;   // (an entry point without colours: null, 0, 0)
+    int color_dtype, CDIM;
+};
+struct View {
+    const float *viewmat;
+    float fx, fy, cx, cy;
+    int W, H;
+    float eps2d, near_plane, far_plane;   // (an entry point without planes: 0, 0 -- nothing downstream of one reads them)
+};
+
+// The frame's SIZE RECORD (ms_render_fwd's host_info: i64 words in pinned memory, written by the scans' total pass and --
+// word 7, between the two halves of a frame -- by the library's host side).  The values are ABI: the header documents some,
+// the Python layer tests others by value (the static_asserts below); only C++ uses the names.
+enum InfoWord {
+    kInfoPairs = 0,      // (Gaussian, tile) pairs in the band: M
+    kInfoMaxCount = 1,   // the longest tile list (binning.hip, count_tail: sizes the exact path's sort classes)
+    kInfoMedium = 2, kInfoLarge = 3, kInfoXL = 4,   // tiles in the medium / large / extra-large sort class
+    kInfoNeed = 5,       // from the device: the PREVIOUS frame's redo counts; after MS_ERR_WORKSPACE: bytes of isect_buf needed
+    kInfoOnGrid = 6,     // Gaussians whose box touches the grid (a pre-culled band: of its candidates)
+    kInfoFlags = 7,
+    kInfoVerdict = 8,    // a deferred clean-up: the rasteriser stores 1 here when a bin asks for the launches (LazyLists::verdict)
+};
+// word 7: the library's own between the two halves of a frame, and what the backward and the caller learn about the frame
+constexpr int64_t
+    kFrameSpeculated = 1,    // emit + rasterise were enqueued before the size record was known: the finishing half checks it
+    kFrameLargeSorted = 2,   // ... with the large sort class among the launches (a frame that has such tiles needs it)
+    kFrameExact = 4,         // redone on the exact path: the lists the caller reads back are laid out by M, not by capacity
+    kFrameSplit = 8,         // 32-px bins cut into block lists: ids are not Gaussian indices, no backward can walk them
+    kFrameNoSplit = 16,      // restarted without the split (4 M block-list slots overflowed int32): a resumed call must agree
+    kFrameLightBet = 32,     // only the short sorts were launched, on the bet that no tile is heavy: holds iff heavy() == 0
+    kFrameDepthCut = 64,     // pairs behind the bins' cut-offs were never written: the exact path cannot finish such a frame
+    kFrameCutoffs = 128,     // the sort launch left cut-offs for the next frame on this record ...
+    kFrameCutoffsBuf = 256,  // ... in this one of the workspace's two buffers (bit 8)
+    kFrameFronts = 512,      // the rasteriser was given lazily sorted fronts: front counts and redo flags are this frame's
+    kFrameLazy = 1024,       // a lazily sorted frame: no merge scratch between keys and ids in the exact layout
+    kFrameBandCulled = 2048, // the band was pre-culled: word 6 counts its candidates, ids are positions in their list
+    kFrameCleanupDeferred = 4096,   // the clean-up launches were left to the finishing half (word 8 says if they are needed)
+    kFrameQuadLists = 8192,  // a differentiable frame's per-quad lists sit behind the ids (4 bytes per pair and quad of a tile)
+    kFrameClaimed = 16384,   // the histogram rows are per-XCD claims: every emit of the frame must read them that way
+    kFrameRowsZeroed = 32768,   // the rasteriser zeroed the backward's rows of raw sums in the workspace: no memset is owed
+    // bits 16-31: the grid the cut-offs belong to (the record may have served another since); bits 32-47: the band's
+    // signature (a rank's share keeps cut-offs for its own rows and clip only)
+    kFrameCutSigMask = 0xffffffffll << 16;
+constexpr int kFrameCutGridShift = 16, kFrameBandSigShift = 32, kFrameCutoffsBufShift = 8;
+static_assert(kInfoPairs == 0 && kInfoXL == 4 && kInfoNeed == 5 && kInfoOnGrid == 6 && kInfoFlags == 7 && kInfoVerdict == 8,
+              "size record: the header and the Python layer index these words by number");
+static_assert(kFrameSpeculated == 1 && kFrameExact == 4 && kFrameSplit == 8 && kFrameLightBet == 32 && kFrameDepthCut == 64 &&
+                  kFrameFronts == 512 && kFrameBandCulled == 2048 && kFrameCleanupDeferred == 4096 && kFrameQuadLists == 8192 &&
+                  kFrameRowsZeroed == 32768,
+              "flag word: mojosplat_hip.h documents bits 2, 13 and 15, mojosplat_amd/*.py tests the others by value");
+static_assert(((kFrameDepthCut | kFrameCutoffs | kFrameCutoffsBuf | kFrameCutSigMask) & 0x3f) == 0,
+              "flag word: _fused.py withdraws the record's word for the cut-offs by keeping bits 0-5 alone");
+// word 5 as the device leaves it: bins the previous frame's clean-up redid because their sorted front was too short ...
+static inline int64_t front_redos(const int64_t *info) { return info[kInfoNeed] & 0xffffffffll; }
+// ... and because their depth cut-off was stale (bits 32-61; bit 62: the regeneration disagreed with the count kernel)
+static inline int64_t cut_redos(const int64_t *info) { return (info[kInfoNeed] >> 32) & 0x3fffffffll; }
+static inline int64_t heavy(const int64_t *info) { return info[kInfoMedium] + info[kInfoLarge] + info[kInfoXL]; }
+
+// binning.hip: ms_project_isect_count that also writes the rasteriser's records (raster_records: N x 48 B, or null;
+// they take g.colors: the frame's colours, 3 channels, f32 or f16)
+int project_isect_count(const Gaussians &g, const View &v, float radius_clip, int tile_size, int row_begin, int row_end,
+                        int tight, float *means2d, float *conics, float *depths, int32_t *radii, void *workspace,
+                        size_t workspace_bytes, int32_t *tile_ranges, int64_t *isect_info, int64_t *isect_info_mirror,
+                        void *raster_records, void *stream, uint32_t cut_stamp = 0,
                         // a PREPARED scene (ms_scene_prepare): bounds of every block of block_size Gaussians, for the band pre-cull
                         const float *block_bounds = nullptr, int block_size = 0);
 
@@ -92,18 +155,12 @@ int project_isect_count(int64_t N, const float *means3d, const float *scales, in
 // entries; the rasteriser appends a tile to redo_list when pixels are still alive at the end of it.
 // what a depth-cut frame's clean-up launches need to bring a dropped Gaussian's record back (host-side: far_regen)
 struct CutInputs {
-    const float *means3d, *scales, *quats, *opacities, *viewmat;
-    const void *colors;
-    int color_f16;
-    float fx, fy, cx, cy;
-    int W, H;
-    float eps2d, near_plane, far_plane;
-    int scales_are_log;
+    Gaussians g;   // (by value: a deferred clean-up keeps the whole struct beyond the enqueuing call -- rasterize.hip, CleanupMemo)
+    View v;
     void *records;
     int tile_size;
     // a band frame: its rows of the binning grid, and -- pre-culled (band_cull) -- the isect workspace that holds its candidate list
     int row_begin, row_end;
-    int64_t N;
     const void *isect_workspace;
     int band_cull;
 };
@@ -143,12 +200,14 @@ struct LazyLists {
 // rasterize.hip: the clean-up launches a frame enqueued with lazy.verdict set left out, on `stream`; `key` = that pointer
 int rasterize_deferred_cleanup(const void *key, void *stream);
 int far_regen(const LazyLists &lazy, int tw, int n_tiles, int64_t cap, void *stream);
+// project_bwd.hip: ms_project_gaussians_bwd_pose behind its checks of the pose output (v_viewmat, or null, as below)
+int project_bwd(const Gaussians &g, const View &v, const int32_t *radii, const float *v_means2d, const float *v_conics,
+                const float *v_depths, float *v_means3d, float *v_scales, float *v_quats, float *v_viewmat, void *pose_scratch,
+                void *stream);
 // project_bwd.hip: the backward projection straight from the backward rasteriser's packed gradient rows
-int project_bwd_from_rows(int64_t N, const float *means3d, const float *scales, int scales_are_log, const float *quats,
-                          const float *viewmat, float fx, float fy, float cx, float cy, int W, int H, float eps2d,
-                          const int32_t *radii, const float *rows, int CDIM, float *v_means3d, float *v_scales,
-                          float *v_quats, float *v_colors, float *v_opacities, void *stream,
-                          const float *raw_rows_opacities = nullptr,    // non-null: rasterize_bwdq.hip's raw sums (radii may be null)
+int project_bwd_from_rows(const Gaussians &g, const View &v, const int32_t *radii, const float *rows, float *v_means3d,
+                          float *v_scales, float *v_quats, float *v_colors, float *v_opacities, void *stream,
+                          bool raw_rows = false,    // rasterize_bwdq.hip's raw sums, finished with g.opacities (radii may be null)
                           // non-null: dL/dviewmat f32[16] (overwritten, bottom row 0) through ms_pose_scratch_bytes(N) of scratch
                           float *v_viewmat = nullptr, void *pose_scratch = nullptr);
 // project_bwd.hip: the checks of a pose-gradient entry point's output and scratch (ms_pose_scratch_bytes)

@@ -35,6 +35,7 @@ extern "C" int ms_project_gaussians_fwd(int64_t N, const float *means3d, const f
                                         float near_plane, float far_plane, float radius_clip,
                                         float *means2d, float *conics, float *depths,
                                         int32_t *radii, void *stream) {
+    const ms::View v{viewmat, fx, fy, cx, cy, W, H, eps2d, near_plane, far_plane};
     MS_REQUIRE(N >= 0, MS_ERR_INVALID_ARG, "project: N < 0");
     if (N == 0) return MS_OK;
     MS_REQUIRE(means3d && scales && quats && viewmat && means2d && conics && depths && radii,
@@ -43,8 +44,7 @@ extern "C" int ms_project_gaussians_fwd(int64_t N, const float *means3d, const f
                "project: bad camera (W=%d H=%d fx=%g fy=%g)", W, H, fx, fy);
     MS_REQUIRE(((uintptr_t)quats & 15) == 0 && ((uintptr_t)means2d & 7) == 0 && ((uintptr_t)radii & 7) == 0,
                MS_ERR_INVALID_ARG, "project: quats must be 16-byte, means2d/radii 8-byte aligned");
-    const ms::ProjParams P = ms::make_proj_params(fx, fy, cx, cy, W, H, eps2d, near_plane, far_plane, radius_clip,
-                                                  scales_are_log, opacities != nullptr);
+    const ms::ProjParams P = ms::make_proj_params(v, radius_clip, scales_are_log, opacities != nullptr);
     const int64_t grid = ms::ceil_div(N, 256);
     MS_REQUIRE(grid <= 0x7fffffff, MS_ERR_INVALID_ARG, "project: N too large");
     hipLaunchKernelGGL(k_project_ewa_fwd, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, N,

@@ -376,29 +376,26 @@ int ms::check_pose_out(int64_t N, const float *out, const void *scratch, size_t 
     return MS_OK;
 }
 
-static int project_bwd_impl(int64_t N, const float *means3d, const float *scales, int scales_are_log, const float *quats,
-                            const float *viewmat, float fx, float fy, float cx, float cy, int W, int H, float eps2d,
-                            const int32_t *radii, const float *v_means2d, const float *v_conics, const float *v_depths,
-                            float *v_means3d, float *v_scales, float *v_quats, float *v_viewmat, void *pose_scratch,
-                            void *stream) {
-    MS_REQUIRE(N >= 0, MS_ERR_INVALID_ARG, "project_bwd: N < 0");
-    if (N == 0) return v_viewmat ? ms::pose_slab_sum(nullptr, 0, 12, v_viewmat, 16, stream) : MS_OK;
-    MS_REQUIRE(means3d && scales && quats && viewmat && radii && v_means2d && v_conics && v_means3d &&
+// (the limits are the forward projection's, from make_proj_params's own expressions)
+static ProjBwdParams proj_bwd_params(const ms::View &v, int scales_are_log) {
+    const ms::ProjParams F = ms::make_proj_params(v, 0.0f, scales_are_log, false);
+    return ProjBwdParams{F.fx, F.fy, F.cx, F.cy, F.eps2d, F.lim_x_pos, F.lim_x_neg, F.lim_y_pos, F.lim_y_neg, scales_are_log};
+}
+
+int ms::project_bwd(const ms::Gaussians &g, const ms::View &v, const int32_t *radii, const float *v_means2d, const float *v_conics,
+                    const float *v_depths, float *v_means3d, float *v_scales, float *v_quats, float *v_viewmat, void *pose_scratch,
+                    void *stream) {
+    MS_REQUIRE(g.N >= 0, MS_ERR_INVALID_ARG, "project_bwd: N < 0");
+    if (g.N == 0) return v_viewmat ? ms::pose_slab_sum(nullptr, 0, 12, v_viewmat, 16, stream) : MS_OK;
+    MS_REQUIRE(g.means3d && g.scales && g.quats && v.viewmat && radii && v_means2d && v_conics && v_means3d &&
                    v_scales && v_quats, MS_ERR_INVALID_ARG, "project_bwd: null pointer");
-    MS_REQUIRE(W > 0 && H > 0 && fx != 0.f && fy != 0.f, MS_ERR_INVALID_ARG, "project_bwd: bad camera");
-    MS_REQUIRE(((uintptr_t)quats & 15) == 0 && ((uintptr_t)v_quats & 15) == 0 && ((uintptr_t)radii & 7) == 0,
+    MS_REQUIRE(v.W > 0 && v.H > 0 && v.fx != 0.f && v.fy != 0.f, MS_ERR_INVALID_ARG, "project_bwd: bad camera");
+    MS_REQUIRE(((uintptr_t)g.quats & 15) == 0 && ((uintptr_t)v_quats & 15) == 0 && ((uintptr_t)radii & 7) == 0,
                MS_ERR_INVALID_ARG, "project_bwd: quats/v_quats must be 16-byte, radii 8-byte aligned");
-    ProjBwdParams P;
-    P.fx = fx; P.fy = fy; P.cx = cx; P.cy = cy; P.eps2d = eps2d;
-    const float tan_fovx = 0.5f * (float)W / fx, tan_fovy = 0.5f * (float)H / fy;
-    P.lim_x_pos = ((float)W - cx) / fx + 0.3f * tan_fovx;
-    P.lim_x_neg = cx / fx + 0.3f * tan_fovx;
-    P.lim_y_pos = ((float)H - cy) / fy + 0.3f * tan_fovy;
-    P.lim_y_neg = cy / fy + 0.3f * tan_fovy;
-    P.scales_are_log = scales_are_log;
-    return launch_ewa_bwd<0, false>(N, v_viewmat, pose_scratch, stream, means3d, scales, quats, viewmat, P, radii, v_means2d,
-                                    v_conics, v_depths, v_means3d, v_scales, v_quats, (const float *)nullptr, 0, (float *)nullptr,
-                                    (float *)nullptr, (const float *)nullptr, DensifyArgs{});
+    const ProjBwdParams P = proj_bwd_params(v, g.scales_are_log);
+    return launch_ewa_bwd<0, false>(g.N, v_viewmat, pose_scratch, stream, g.means3d, g.scales, g.quats, v.viewmat, P, radii,
+                                    v_means2d, v_conics, v_depths, v_means3d, v_scales, v_quats, (const float *)nullptr, 0,
+                                    (float *)nullptr, (float *)nullptr, (const float *)nullptr, DensifyArgs{});
 }
 
 extern "C" int ms_project_gaussians_bwd(int64_t N, const float *means3d, const float *scales,
@@ -408,8 +405,9 @@ extern "C" int ms_project_gaussians_bwd(int64_t N, const float *means3d, const f
                                         const float *v_conics, const float *v_depths,
                                         float *v_means3d, float *v_scales, float *v_quats,
                                         void *stream) {
-    return project_bwd_impl(N, means3d, scales, scales_are_log, quats, viewmat, fx, fy, cx, cy, W, H, eps2d, radii, v_means2d,
-                            v_conics, v_depths, v_means3d, v_scales, v_quats, nullptr, nullptr, stream);
+    const ms::Gaussians g{N, means3d, scales, scales_are_log, quats, nullptr, nullptr, 0, 0};
+    const ms::View v{viewmat, fx, fy, cx, cy, W, H, eps2d, 0.f, 0.f};
+    return ms::project_bwd(g, v, radii, v_means2d, v_conics, v_depths, v_means3d, v_scales, v_quats, nullptr, nullptr, stream);
 }
 
 extern "C" int ms_project_gaussians_bwd_pose(int64_t N, const float *means3d, const float *scales, int scales_are_log,
@@ -418,76 +416,61 @@ extern "C" int ms_project_gaussians_bwd_pose(int64_t N, const float *means3d, co
                                              const float *v_conics, const float *v_depths, float *v_means3d, float *v_scales,
                                              float *v_quats, float *v_viewmat, void *pose_scratch, size_t pose_scratch_bytes,
                                              void *stream) {
+    const ms::Gaussians g{N, means3d, scales, scales_are_log, quats, nullptr, nullptr, 0, 0};
+    const ms::View v{viewmat, fx, fy, cx, cy, W, H, eps2d, 0.f, 0.f};
     if (v_viewmat)
         if (int rc = ms::check_pose_out(N, v_viewmat, pose_scratch, pose_scratch_bytes, "project_bwd")) return rc;
-    return project_bwd_impl(N, means3d, scales, scales_are_log, quats, viewmat, fx, fy, cx, cy, W, H, eps2d, radii, v_means2d,
-                            v_conics, v_depths, v_means3d, v_scales, v_quats, v_viewmat, pose_scratch, stream);
+    return ms::project_bwd(g, v, radii, v_means2d, v_conics, v_depths, v_means3d, v_scales, v_quats, v_viewmat, pose_scratch,
+                            stream);
 }
 
 // ms_render_bwd: the same backward straight from the backward rasteriser's packed rows (which it also unpacks into
 // v_colors / v_opacities)
-int ms::project_bwd_from_rows(int64_t N, const float *means3d, const float *scales, int scales_are_log, const float *quats,
-                              const float *viewmat, float fx, float fy, float cx, float cy, int W, int H, float eps2d,
-                              const int32_t *radii, const float *rows, int CDIM, float *v_means3d, float *v_scales,
-                              float *v_quats, float *v_colors, float *v_opacities, void *stream, const float *raw_rows_opacities,
-                              float *v_viewmat, void *pose_scratch) {
-    if (N == 0) return v_viewmat ? ms::pose_slab_sum(nullptr, 0, 12, v_viewmat, 16, stream) : MS_OK;
-    const bool raw = raw_rows_opacities != nullptr;   // the quad-wave rasteriser's raw sums (ROWS == 2)
-    MS_REQUIRE(means3d && scales && quats && viewmat && (radii || raw) && rows && v_means3d && v_scales && v_quats && v_colors && v_opacities,
+int ms::project_bwd_from_rows(const ms::Gaussians &g, const ms::View &v, const int32_t *radii, const float *rows,
+                              float *v_means3d, float *v_scales, float *v_quats, float *v_colors, float *v_opacities,
+                              void *stream, bool raw, float *v_viewmat, void *pose_scratch) {
+    if (g.N == 0) return v_viewmat ? ms::pose_slab_sum(nullptr, 0, 12, v_viewmat, 16, stream) : MS_OK;
+    // raw: the quad-wave rasteriser's raw sums (ROWS == 2)
+    MS_REQUIRE(g.means3d && g.scales && g.quats && v.viewmat && (radii || raw) && rows && v_means3d && v_scales && v_quats && v_colors && v_opacities,
                MS_ERR_INVALID_ARG, "project_bwd: null pointer");
-    MS_REQUIRE(!raw || CDIM == 3, MS_ERR_INVALID_ARG, "project_bwd: raw rows carry three channels");
-    MS_REQUIRE(W > 0 && H > 0 && fx != 0.f && fy != 0.f && CDIM >= 1 && CDIM <= 4, MS_ERR_INVALID_ARG, "project_bwd: bad camera / channels");
-    MS_REQUIRE(((uintptr_t)quats & 15) == 0 && ((uintptr_t)v_quats & 15) == 0 && ((uintptr_t)radii & 7) == 0 && ((uintptr_t)rows & 15) == 0,
+    MS_REQUIRE(!raw || g.CDIM == 3, MS_ERR_INVALID_ARG, "project_bwd: raw rows carry three channels");
+    MS_REQUIRE(v.W > 0 && v.H > 0 && v.fx != 0.f && v.fy != 0.f && g.CDIM >= 1 && g.CDIM <= 4, MS_ERR_INVALID_ARG, "project_bwd: bad camera / channels");
+    MS_REQUIRE(((uintptr_t)g.quats & 15) == 0 && ((uintptr_t)v_quats & 15) == 0 && ((uintptr_t)radii & 7) == 0 && ((uintptr_t)rows & 15) == 0,
                MS_ERR_INVALID_ARG, "project_bwd: quats / v_quats / rows must be 16-byte, radii 8-byte aligned");
-    ProjBwdParams P;
-    P.fx = fx; P.fy = fy; P.cx = cx; P.cy = cy; P.eps2d = eps2d;
-    const float tan_fovx = 0.5f * (float)W / fx, tan_fovy = 0.5f * (float)H / fy;
-    P.lim_x_pos = ((float)W - cx) / fx + 0.3f * tan_fovx;
-    P.lim_x_neg = cx / fx + 0.3f * tan_fovx;
-    P.lim_y_pos = ((float)H - cy) / fy + 0.3f * tan_fovy;
-    P.lim_y_neg = cy / fy + 0.3f * tan_fovy;
-    P.scales_are_log = scales_are_log;
+    const ProjBwdParams P = proj_bwd_params(v, g.scales_are_log);
     const float *none = nullptr;
     if (raw)
-        return launch_ewa_bwd<2, false>(N, v_viewmat, pose_scratch, stream, means3d, scales, quats, viewmat, P, radii, none, none,
-                                        none, v_means3d, v_scales, v_quats, rows, CDIM, v_colors, v_opacities, raw_rows_opacities,
+        return launch_ewa_bwd<2, false>(g.N, v_viewmat, pose_scratch, stream, g.means3d, g.scales, g.quats, v.viewmat, P, radii, none,
+                                        none, none, v_means3d, v_scales, v_quats, rows, g.CDIM, v_colors, v_opacities, g.opacities,
                                         DensifyArgs{});
-    return launch_ewa_bwd<1, false>(N, v_viewmat, pose_scratch, stream, means3d, scales, quats, viewmat, P, radii, none, none, none,
-                                    v_means3d, v_scales, v_quats, rows, CDIM, v_colors, v_opacities, none, DensifyArgs{});
+    return launch_ewa_bwd<1, false>(g.N, v_viewmat, pose_scratch, stream, g.means3d, g.scales, g.quats, v.viewmat, P, radii, none,
+                                    none, none, v_means3d, v_scales, v_quats, rows, g.CDIM, v_colors, v_opacities, none, DensifyArgs{});
 }
 
 // ms_render_bwd_finish with the densification statistics: k_project_ewa_bwd<2, true>
-static int finish_densify_impl(int64_t N, const float *means3d, const float *scales, int scales_are_log, const float *quats,
-                               const float *opacities, int CDIM, const float *viewmat, float fx, float fy, float cx, float cy,
-                               int W, int H, float eps2d, const float *rows, float *v_means3d, float *v_scales, float *v_quats,
-                               float *v_opacities, float *v_colors, float near_plane, float far_plane, float *grad2d,
-                               float *count, float *max_radii, float *v_viewmat, void *pose_scratch, void *stream) {
-    MS_REQUIRE(N >= 0 && CDIM == 3 && v_means3d && v_scales && v_quats && v_opacities && v_colors && grad2d && count && max_radii,
+static int finish_densify_impl(const ms::Gaussians &g, const ms::View &v, const float *rows, float *v_means3d, float *v_scales,
+                               float *v_quats, float *v_opacities, float *v_colors, float *grad2d, float *count,
+                               float *max_radii, float *v_viewmat, void *pose_scratch, void *stream) {
+    MS_REQUIRE(g.N >= 0 && g.CDIM == 3 && v_means3d && v_scales && v_quats && v_opacities && v_colors && grad2d && count && max_radii,
                MS_ERR_INVALID_ARG, "render_bwd_finish_densify: bad argument");
-    if (N == 0) return v_viewmat ? ms::pose_slab_sum(nullptr, 0, 12, v_viewmat, 16, stream) : MS_OK;
-    MS_REQUIRE(means3d && scales && quats && viewmat && rows && opacities, MS_ERR_INVALID_ARG,
+    if (g.N == 0) return v_viewmat ? ms::pose_slab_sum(nullptr, 0, 12, v_viewmat, 16, stream) : MS_OK;
+    MS_REQUIRE(g.means3d && g.scales && g.quats && v.viewmat && rows && g.opacities, MS_ERR_INVALID_ARG,
                "render_bwd_finish_densify: null pointer");
-    MS_REQUIRE(W > 0 && H > 0 && fx != 0.f && fy != 0.f, MS_ERR_INVALID_ARG, "render_bwd_finish_densify: bad camera");
-    MS_REQUIRE(((uintptr_t)quats & 15) == 0 && ((uintptr_t)v_quats & 15) == 0 && ((uintptr_t)rows & 15) == 0,
+    MS_REQUIRE(v.W > 0 && v.H > 0 && v.fx != 0.f && v.fy != 0.f, MS_ERR_INVALID_ARG, "render_bwd_finish_densify: bad camera");
+    MS_REQUIRE(((uintptr_t)g.quats & 15) == 0 && ((uintptr_t)v_quats & 15) == 0 && ((uintptr_t)rows & 15) == 0,
                MS_ERR_INVALID_ARG, "render_bwd_finish_densify: quats / v_quats / rows must be 16-byte aligned");
     MS_REQUIRE((((uintptr_t)grad2d | (uintptr_t)count | (uintptr_t)max_radii) & 3) == 0, MS_ERR_INVALID_ARG,
                "render_bwd_finish_densify: statistics must be 4-byte aligned");
-    ProjBwdParams P;
-    P.fx = fx; P.fy = fy; P.cx = cx; P.cy = cy; P.eps2d = eps2d;
-    const float tan_fovx = 0.5f * (float)W / fx, tan_fovy = 0.5f * (float)H / fy;
-    P.lim_x_pos = ((float)W - cx) / fx + 0.3f * tan_fovx;
-    P.lim_x_neg = cx / fx + 0.3f * tan_fovx;
-    P.lim_y_pos = ((float)H - cy) / fy + 0.3f * tan_fovy;
-    P.lim_y_neg = cy / fy + 0.3f * tan_fovy;
-    P.scales_are_log = scales_are_log;
+    const ProjBwdParams P = proj_bwd_params(v, g.scales_are_log);
     DensifyArgs D;
     // the frame's projection: its planes, the opacity-aware extent and no radius clip (pipeline.hip, ms_render_fwd)
-    D.P = ms::make_proj_params(fx, fy, cx, cy, W, H, eps2d, near_plane, far_plane, 0.0f, scales_are_log, true);
-    D.half_w = 0.5f * (float)W; D.half_h = 0.5f * (float)H; D.max_wh = (float)(W > H ? W : H);
+    D.P = ms::make_proj_params(v, 0.0f, g.scales_are_log, true);
+    D.half_w = 0.5f * (float)v.W; D.half_h = 0.5f * (float)v.H; D.max_wh = (float)(v.W > v.H ? v.W : v.H);
     D.grad2d = grad2d; D.count = count; D.max_radii = max_radii;
     const float *none = nullptr;
-    return launch_ewa_bwd<2, true>(N, v_viewmat, pose_scratch, stream, means3d, scales, quats, viewmat, P, (const int32_t *)nullptr,
-                                   none, none, none, v_means3d, v_scales, v_quats, rows, CDIM, v_colors, v_opacities, opacities, D);
+    return launch_ewa_bwd<2, true>(g.N, v_viewmat, pose_scratch, stream, g.means3d, g.scales, g.quats, v.viewmat, P,
+                                   (const int32_t *)nullptr, none, none, none, v_means3d, v_scales, v_quats, rows, g.CDIM, v_colors,
+                                   v_opacities, g.opacities, D);
 }
 
 extern "C" int ms_render_bwd_finish_densify(int64_t N, const float *means3d, const float *scales, int scales_are_log,
@@ -496,9 +479,10 @@ extern "C" int ms_render_bwd_finish_densify(int64_t N, const float *means3d, con
                                             const float *rows, float *v_means3d, float *v_scales, float *v_quats,
                                             float *v_opacities, float *v_colors, float near_plane, float far_plane,
                                             float *grad2d, float *count, float *max_radii, void *stream) {
-    return finish_densify_impl(N, means3d, scales, scales_are_log, quats, opacities, CDIM, viewmat, fx, fy, cx, cy, W, H, eps2d, rows,
-                               v_means3d, v_scales, v_quats, v_opacities, v_colors, near_plane, far_plane, grad2d, count,
-                               max_radii, nullptr, nullptr, stream);
+    const ms::Gaussians g{N, means3d, scales, scales_are_log, quats, opacities, nullptr, 0, CDIM};
+    const ms::View v{viewmat, fx, fy, cx, cy, W, H, eps2d, near_plane, far_plane};
+    return finish_densify_impl(g, v, rows, v_means3d, v_scales, v_quats, v_opacities, v_colors, grad2d, count, max_radii, nullptr,
+                               nullptr, stream);
 }
 
 extern "C" int ms_render_bwd_finish_densify_pose(int64_t N, const float *means3d, const float *scales, int scales_are_log,
@@ -508,11 +492,12 @@ extern "C" int ms_render_bwd_finish_densify_pose(int64_t N, const float *means3d
                                                  float *v_opacities, float *v_colors, float near_plane, float far_plane,
                                                  float *grad2d, float *count, float *max_radii, float *v_viewmat,
                                                  void *pose_scratch, size_t pose_scratch_bytes, void *stream) {
+    const ms::Gaussians g{N, means3d, scales, scales_are_log, quats, opacities, nullptr, 0, CDIM};
+    const ms::View v{viewmat, fx, fy, cx, cy, W, H, eps2d, near_plane, far_plane};
     if (v_viewmat)
         if (int rc = ms::check_pose_out(N, v_viewmat, pose_scratch, pose_scratch_bytes, "render_bwd_finish_densify")) return rc;
-    return finish_densify_impl(N, means3d, scales, scales_are_log, quats, opacities, CDIM, viewmat, fx, fy, cx, cy, W, H, eps2d, rows,
-                               v_means3d, v_scales, v_quats, v_opacities, v_colors, near_plane, far_plane, grad2d, count,
-                               max_radii, v_viewmat, pose_scratch, stream);
+    return finish_densify_impl(g, v, rows, v_means3d, v_scales, v_quats, v_opacities, v_colors, grad2d, count, max_radii, v_viewmat,
+                               pose_scratch, stream);
 }
 
 extern "C" int ms_densify_stats_update(int64_t N, int W, int H, const int32_t *radii, const float *v_means2d, float *grad2d,

@@ -20,13 +20,13 @@ struct ProjOut {
     int r0, r1;
 };
 
-static inline ProjParams make_proj_params(float fx, float fy, float cx, float cy, int W, int H, float eps2d,
-                                          float near_plane, float far_plane, float radius_clip,
-                                          int scales_are_log, bool has_opacity) {
+static inline ProjParams make_proj_params(const View &v, float radius_clip, int scales_are_log, bool has_opacity) {
+    const float fx = v.fx, fy = v.fy, cx = v.cx, cy = v.cy;
+    const int W = v.W, H = v.H;
     ProjParams P;
     P.fx = fx; P.fy = fy; P.cx = cx; P.cy = cy;
     P.W = (float)W; P.H = (float)H;
-    P.eps2d = eps2d; P.near_plane = near_plane; P.far_plane = far_plane; P.radius_clip = radius_clip;
+    P.eps2d = v.eps2d; P.near_plane = v.near_plane; P.far_plane = v.far_plane; P.radius_clip = radius_clip;
     const float tan_fovx = 0.5f * (float)W / fx, tan_fovy = 0.5f * (float)H / fy;
     P.lim_x_pos = ((float)W - cx) / fx + 0.3f * tan_fovx;
     P.lim_x_neg = cx / fx + 0.3f * tan_fovx;

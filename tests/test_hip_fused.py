@@ -760,7 +760,9 @@ def test_depth_cut_frames_equal_uncut_frames(device, monkeypatch, N, W, H, ell, 
     their bin ended (csrc/binning.hip, k_project_hist; forced here whatever the scene's size: MOJOSPLAT_DEPTH_CUT=2).
     Bit for bit the uncut frames (MOJOSPLAT_DEPTH_CUT=0): on a still camera, along an orbit, and across a swap to a scene
     whose near Gaussians have all but vanished -- stale cut-offs that leave bins short of pairs, which the clean-up
-    launches regenerate from the box records (rasterize.hip, k_far_regen) -- and back."""
+    launches regenerate from the box records (rasterize.hip, k_far_regen) -- and back.  "denser": the same Gaussians
+    at twice the size, three to four times the pairs on the same grid and scratch -- a frame that starts with the cut
+    outgrows the intersection buffer and is started over without it."""
     bg = torch.tensor(BACKGROUND_V1, device=device)
     sc, cam = randscene_v1(N, W, H, ell=ell, seed=42, device=device)   # (a scene whose sorted fronts saturate its pixels)
     faint = dict(sc)
@@ -774,6 +776,9 @@ def test_depth_cut_frames_equal_uncut_frames(device, monkeypatch, N, W, H, ell, 
     if px == 32:   # a larger scene on the same grid: the lane's scratch is reallocated, its cut-offs with it
         big, _ = randscene_v1(N + N // 2, W, H, ell=ell, seed=43, device=device)
         sequences["grow"] = [(sc, cam)] * 3 + [(big, cam)] * 4
+        denser = dict(sc)
+        denser["scales"] = sc["scales"] + math.log(2.0)
+        sequences["denser"] = [(sc, cam)] * 3 + [(denser, cam)] * 2
 
     def run(mode, seq):
         _hip_mod.config_depth_cut(int(mode))
@@ -799,6 +804,10 @@ def test_depth_cut_frames_equal_uncut_frames(device, monkeypatch, N, W, H, ell, 
             assert st.get("cut_redo_tiles", 0) == 0, (label, st)   # the cut-offs hold while the view changes slowly
         elif label == "swap":
             assert st.get("cut_redo_tiles", 0) > 0, st                # ... and the swap is what the fallback is for
+        elif label == "denser":
+            # (the frames before the denser ones took the cut -- the count above -- and left the record a cut frame starts
+            # from; the first denser frame overflowed a buffer grown with 1.25 slack for a third of its pairs)
+            assert st.get("overflow", 0) >= 1, st
     # the first frame of a sequence is the per-stage path's (an uncut frame of the fused path is tested to be)
     assert torch.equal(ref[0], stagewise(sc, cam, bg, 16))
     _fused._state.clear()
@@ -810,7 +819,10 @@ def test_depth_cut_on_band_frames(device, px, world):
     record's signature), the count kernel's deferred records and the regeneration launches working on POSITIONS of the
     band's pre-culled candidate list.  Every band's frames with the cut forced equal its frames without, bit for bit --
     still camera, orbit, and a swap to a scene whose near half has all but vanished (stale cut-offs: bins get their pairs
-    back from k_far_regen by position) -- and the bands of the first frame assemble the per-stage path's image."""
+    back from k_far_regen by position) -- and the bands of the first frame assemble the per-stage path's image.  The last
+    two frames hold the same Gaussians at twice the size: a band's cut frame that outgrows its intersection buffer is
+    started over without the cut, its rows handed back in the units the caller gave them.  (Three more frames of the scene
+    come before them: the swap leaves the lane on full sorts for four frames, which take no cut and leave no cut-offs.)"""
     from mojosplat_amd.distributed import band_plan
     N, W, H, ell = 400_000, 1280, 720, (-3.5 if px != 64 else -3.0)
     bg = torch.tensor(BACKGROUND_V1, device=device)
@@ -818,12 +830,14 @@ def test_depth_cut_on_band_frames(device, px, world):
     faint = dict(sc)
     depth = (sc["means3d"] @ cam.R.T + cam.T)[:, 2]
     faint["opacities"] = torch.where(depth < depth.median(), sc["opacities"] * 0.02, sc["opacities"])
-    seq = [(sc, cam)] * 4 + [(sc, _orbit(cam, 0.004 * i)) for i in range(1, 5)] + [(faint, cam)] * 3 + [(sc, cam)] * 2
+    denser = dict(sc)
+    denser["scales"] = sc["scales"] + math.log(2.0)
+    seq = [(sc, cam)] * 4 + [(sc, _orbit(cam, 0.004 * i)) for i in range(1, 5)] + [(faint, cam)] * 3 + [(sc, cam)] * 5 + [(denser, cam)] * 2
     th16 = -(-H // 16)
     _, bands = band_plan(th16, world)
     ref0 = stagewise(sc, cam, bg, 16)
     assembled = torch.zeros_like(ref0)
-    totals = {}
+    totals, primed = {}, 0
     try:
         for r0, r1 in bands:
             y0, y1 = r0 * 16, min(r1 * 16, H)
@@ -832,19 +846,22 @@ def test_depth_cut_on_band_frames(device, px, world):
                 _hip_mod.config_depth_cut(int(mode))
                 _fused._state.clear()
                 _fused.FRAME_STATS = st = {}
-                frames, culled = [], 0
+                frames, culled, flags = [], 0, []
                 for s_, c_ in seq:
                     buf = torch.zeros((H, W, 3), device=device)
                     info = {}
                     _fused.render_fwd_hip(s_["means3d"], s_["scales"], s_["quats"], s_["opacities"], s_["features"], c_, bg, px,
                                           row_range=(r0, r1), out=buf, info=info, rows16=(px != 16))
                     culled += 1 if info["flags"] & 2048 else 0
+                    flags.append(info["flags"])
                     frames.append(buf[y0:y1].clone())
                 torch.cuda.synchronize()
                 _fused.FRAME_STATS = None
-                return frames, st, culled
-            ref, st0, _ = run(0)
-            got, st, culled = run(2)
+                return frames, st, culled, flags
+            ref, st0, _, _ = run(0)
+            got, st, culled, flags = run(2)
+            # (bits 6 and 7 of the flag word: the frame took the cut and left cut-offs -- the next frame starts as a cut frame)
+            primed += 1 if (flags[-3] & 64) and (flags[-3] & 128) else 0
             assert st0.get("depth_cut", 0) == 0, (r0, r1, st0)   # (a sparse edge band has no heavy bin and takes no cut: the total below)
             assert culled == len(seq), "the bands of this test are pre-culled"
             assert st.get("regen_mismatch", 0) == 0, st
@@ -859,6 +876,8 @@ def test_depth_cut_on_band_frames(device, px, world):
     assert torch.equal(assembled, ref0)
     assert totals.get("depth_cut", 0) >= 4 * (world // 2), totals   # at least the centre bands cut most of their frames
     assert totals.get("cut_redo_tiles", 0) > 0, totals   # the swap did strand bins whose cut-offs were stale
+    assert primed >= 1, "the frame before the denser ones took the cut in no band"
+    assert totals.get("overflow", 0) >= 1, totals   # the denser frames outgrew a buffer sized with 1.25 slack for a third of their pairs
 
 
 @pytest.mark.parametrize("seed", range(6))
