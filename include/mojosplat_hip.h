@@ -72,7 +72,8 @@ extern "C" {
 
 #define MS_ABI_VERSION 5   /* 2: ms_render_bwd takes the frame's image (render_colors); 3: ms_render_redo_counts, the band-frame pair, ms_scene_prepare;
                               4: the pose-gradient entry points (ms_pose_scratch_bytes, ms_*_pose); 5: ms_adam_step
-                              (the ms_densify_*, ms_mcmc_*, ms_knn* and ms_ply_* entry points were added under 5: new symbols, nothing existing changed) */
+                              (the ms_densify_*, ms_mcmc_*, ms_knn* and ms_ply_* entry points, ms_config_fused_sort, ms_render_front_count_offset and bit 48
+                              of the flag word were added under 5: new symbols and a new bit, nothing existing changed) */
 
 typedef enum ms_status {
     MS_OK = 0,
@@ -265,6 +266,10 @@ int ms_project_gaussians_bwd(int64_t N, const float *means3d, const float *scale
  * a negative argument leaves that setting alone.  Process-wide; the defaults come from MOJOSPLAT_DEPTH_CUT /
  * MOJOSPLAT_DEPTH_CUT_MIN_PAIRS, read once.  (For tests and measurements that switch inside one process.) */
 int ms_config_depth_cut(int mode, long long min_pairs);
+/* Sort + rasterise in one launch (whole forward frames on plain 32-px bins): mode 0 never / 1 where the rasteriser runs two
+ * waves a block by its own rule (default) / 2 on every such frame; < 0 leaves it.  MOJOSPLAT_FUSED_SORT in the environment is
+ * read once; this changes the setting in-process.  The image is the same whatever the mode. */
+int ms_config_fused_sort(int mode);
 
 /* ms_render_bwd in two halves, for a multi-GPU rank's differentiable BAND frame (a 3-channel frame at a tile size that is a
  * multiple of 16, rendered with render_alphas over tile rows [tile_row_begin, tile_row_end) -- or the whole frame: 0, tile_h):
@@ -617,6 +622,9 @@ int ms_render_band_finish(const ms_band_frame *frame, const ms_band_lane *lane, 
  * capacity = (isect_bytes - 768) / (12 + 4 q) on the sync-free path, + align256(4 q M) bytes on the exact one (the size
  * ms_render_fwd asks for in host_info[5] includes them). */
 int ms_render_workspace_layout(int64_t N, int tile_w, int tile_h, size_t *offsets);
+/* Byte offset, in a frame's workspace, of its per-tile front counts (tile_w * tile_h int32: how many entries of a list
+ * beyond 1024 are sorted; undefined for shorter lists).  For tests and measurements. */
+int ms_render_front_count_offset(int64_t N, int tile_w, int tile_h, size_t *offset);
 
 /* ms_isect_tiles_emit without the host knowing M: `isect_info_dev` is the DEVICE record written
  * by ms_isect_tiles_count, `capacity` the number of entries sort_keys / flatten_ids can hold.

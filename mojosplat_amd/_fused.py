@@ -138,6 +138,7 @@ def _grow(st, key, nbytes, dev, slack=1.0):
 #   cut_redo_tiles    ... because their depth cut-off was: their dropped pairs were regenerated (likewise)
 #   depth_cut         frames that dropped the pairs behind their bins' depth cut-offs
 #   regen_mismatch    frames whose clean-up launches brought back a pair the count kernel had not counted (a bug if ever > 0)
+#   fused_sort        frames whose bins were sorted by the workgroups that rasterised them (one launch for both)
 #   front_level_up / full_sort_on   the lane's lazy-sorting mode escalated
 #   lazy_sort_retry   a lane on full sorts tried lazily sorted fronts again
 FRAME_STATS = None
@@ -173,6 +174,8 @@ def _count_frame(stats, frame, host, grew, counts_valid=True):
             stats["regen_mismatch"] = stats.get("regen_mismatch", 0) + 1
     if flags & 64:
         stats["depth_cut"] = stats.get("depth_cut", 0) + 1
+    if (flags & 281474976710656) and not (flags & 4):   # bit 48: the sort launch rode in the rasteriser (k_sort_rasterize)
+        stats["fused_sort"] = stats.get("fused_sort", 0) + 1
     if (flags & 4096) and not (flags & 4):   # the band pair left the clean-up launches to its finishing half (_band.py)
         stats["cleanup_deferred"] = stats.get("cleanup_deferred", 0) + 1
         if len(host) > 8 and int(host[8]) != 0:   # ... which found the rasteriser asking for them
@@ -505,6 +508,25 @@ def last_frame_list_entries(dev, N, tile_w, tile_h, lane=0):
     nb = tile_w * tile_h * 8
     r = st["ws"][off[4]:off[4] + nb].view(torch.int32).view(tile_h, tile_w, 2)
     return int((r[..., 1] - r[..., 0]).clamp_min(0).sum())
+
+
+def last_frame_lists(dev, N, tile_w, tile_h, lane=0):
+    """-> (ranges int32 (tile_h, tile_w, 2), front_count int32 (tile_h, tile_w)): copies of what the LAST frame on
+    (dev, lane) left in its workspace for the tile_w x tile_h grid of its tile size.  A front count means something only
+    for a list of more than 1024 entries of a lazily sorted frame.  Synchronises; for tests."""
+    st = _state.get((dev, lane))
+    if st is None or st.get("ws") is None:
+        raise RuntimeError("no frame has been rendered on this lane")
+    L = _hip.lib()
+    off = (ctypes.c_size_t * 6)()
+    _hip.check(L.ms_render_workspace_layout(N, tile_w, tile_h, off), "ms_render_workspace_layout")
+    foff = ctypes.c_size_t()
+    _hip.check(L.ms_render_front_count_offset(N, tile_w, tile_h, ctypes.byref(foff)), "ms_render_front_count_offset")
+    torch.cuda.synchronize(dev)
+    T = tile_w * tile_h
+    ranges = st["ws"][off[4]:off[4] + T * 8].view(torch.int32).view(tile_h, tile_w, 2).clone()
+    fronts = st["ws"][foff.value:foff.value + T * 4].view(torch.int32).view(tile_h, tile_w).clone()
+    return ranges, fronts
 
 
 def render_begin_hip(means3d, scales, quats, opacities, colors, camera, background, tile_size,

@@ -56,8 +56,10 @@ _SIGNATURES = {
                               c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
                               c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ms_render_workspace_layout": (c_int, [c_int64, c_int, c_int, c_void_p]),
+    "ms_render_front_count_offset": (c_int, [c_int64, c_int, c_int, c_void_p]),
     "ms_render_bwd_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "ms_config_depth_cut": (c_int, [c_int, ctypes.c_longlong]),
+    "ms_config_fused_sort": (c_int, [c_int]),
     "ms_render_redo_counts": (c_int, [c_void_p, c_size_t, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "ms_render_bwd": (c_int, [c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_float,
                               c_float, c_float, c_float, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_size_t,
@@ -356,3 +358,11 @@ def config_depth_cut(mode=None, min_pairs=None):
     inside one process call this instead of writing os.environ."""
     check(lib().ms_config_depth_cut(-1 if mode is None else int(mode), -1 if min_pairs is None else int(min_pairs)),
           "ms_config_depth_cut")
+
+
+def config_fused_sort(mode=None):
+    """Sort + rasterise in one launch (include/mojosplat_hip.h, ms_config_fused_sort): mode 0 never / 1 where the
+    rasteriser runs two waves a block by its own rule (the default) / 2 on every whole frame of plain 32-px bins.
+    Process-wide; None leaves it alone.  The library reads MOJOSPLAT_FUSED_SORT once -- tests and measurements that
+    switch inside one process call this instead of writing os.environ."""
+    check(lib().ms_config_fused_sort(-1 if mode is None else int(mode)), "ms_config_fused_sort")

@@ -2729,7 +2729,9 @@ int emit_impl(int64_t N, const float *means2d, const int32_t *radii, const float
               int tile_w, int tile_h, int row_begin, int row_end, void *workspace, size_t workspace_bytes,
               const int32_t *tile_ranges, const int64_t *host_info, const int64_t *info_dev, int64_t cap,
               uint64_t *sort_keys, uint64_t *sort_tmp, int32_t *flatten_ids, int64_t *isect_ids,
-              hipStream_t stream, const ms::BlockLists *blocks = nullptr, const ms::DeferredTotal *defer = nullptr) {
+              hipStream_t stream, const ms::BlockLists *blocks = nullptr, const ms::DeferredTotal *defer = nullptr,
+              ms::FusedSort *fuse = nullptr) {
+    if (fuse) fuse->taken = 0;
     const ms::BlockLists bl = blocks ? *blocks : ms::BlockLists{nullptr, nullptr, nullptr, 0, 0};
     const uint32_t cut_stamp = defer ? defer->cut_stamp : 0u;   // != 0: a depth-cut frame (k_project_hist)
     // bits 4-5 of `lazy` (ms_render_fwd only): the merged sort launch leaves the NEXT frame's cut-offs in buffer (lazy >> 4) & 1;
@@ -2840,6 +2842,15 @@ int emit_impl(int64_t N, const float *means2d, const int32_t *radii, const float
             const ms::FrontParams fp = ms::front_params(tile_size, lazy, depth_near, depth_far, merged, bl.block_ids != nullptr);
             const uint32_t fixed_min = fp.fixed_min;
             const int fixed_shift = fp.fixed_shift, front_k = fp.front_k, front_cap = fp.front_cap;
+            // The rasteriser sorts each bin in the workgroup that rasterises it (rasterize.hip, k_sort_rasterize): the merged
+            // launch on 32-px bins at the default front depth (2048 keys of LDS room) is left to it, with what it would have taken
+            if (fuse && merged && spec && tile_size == 32 && front_cap <= 2048) {
+                *fuse = ms::FusedSort{1, fp, (const uint32_t *)(ws + p.off_depth_wg), p.G, (const int32_t *)(ws + p.off_order), p.T_local,
+                                      write_tau ? (uint32_t *)(ws + p.off_tau) + (size_t)tau_out * p.T : nullptr,
+                                      (const uint32_t *)(ws + p.off_tau) + (size_t)(1 - tau_out) * p.T, (const uint32_t *)(ws + p.off_has_far),
+                                      cut_stamp, cap, sort_keys, flatten_ids, (int32_t *)(ws + p.off_front)};
+                return MS_OK;
+            }
             size_t front_lds = kFrontLds - (size_t)(kFrontCap - front_cap) * 8;
             // (merged launch: room for eight waves' private sorts of light lists)
             const bool light = merged;
@@ -2956,7 +2967,7 @@ int ms::isect_emit_speculative(int64_t N, const float *means2d, const int32_t *r
                                size_t workspace_bytes, const int32_t *tile_ranges, const int64_t *isect_info_dev,
                                int64_t capacity, const int64_t *prev_info_host, int tight, int lazy, float depth_near,
                                float depth_far, uint64_t *sort_keys, int32_t *flatten_ids,
-                               const ms::DeferredTotal *defer, void *stream_) {
+                               const ms::DeferredTotal *defer, void *stream_, ms::FusedSort *fuse) {
     MS_REQUIRE(N >= 0 && isect_info_dev && capacity > 0 && capacity <= 0x7fffffffll, MS_ERR_INVALID_ARG,
                "isect_emit_speculative: bad N / info / capacity");
     if (int rc = check_grid(tile_size, tile_w, tile_h, row_begin, row_end)) return rc;
@@ -2964,7 +2975,7 @@ int ms::isect_emit_speculative(int64_t N, const float *means2d, const int32_t *r
                MS_ERR_INVALID_ARG, "isect_emit_speculative: null pointer");
     return emit_impl(N, means2d, radii, depths, tight, lazy, depth_near, depth_far, tile_size, tile_w, tile_h,
                      row_begin, row_end, workspace, workspace_bytes, tile_ranges, prev_info_host, isect_info_dev, capacity,
-                     sort_keys, nullptr, flatten_ids, nullptr, (hipStream_t)stream_, nullptr, defer);
+                     sort_keys, nullptr, flatten_ids, nullptr, (hipStream_t)stream_, nullptr, defer, fuse);
 }
 
 int ms::isect_emit_exact(int64_t N, const float *means2d, const int32_t *radii, const float *depths, int tile_size,

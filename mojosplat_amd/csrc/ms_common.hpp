@@ -126,7 +126,11 @@ constexpr int64_t
     kFrameRowsZeroed = 32768,   // the rasteriser zeroed the backward's rows of raw sums in the workspace: no memset is owed
     // bits 16-31: the grid the cut-offs belong to (the record may have served another since); bits 32-47: the band's
     // signature (a rank's share keeps cut-offs for its own rows and clip only)
-    kFrameCutSigMask = 0xffffffffll << 16;
+    kFrameCutSigMask = 0xffffffffll << 16,
+    // bit 48: the frame's sort launch rode in its rasteriser (rasterize.hip, k_sort_rasterize): one workgroup per 32-px bin sorted
+    // the bin's list and rasterised its four blocks.  Nothing downstream reads the lists differently -- the bit exists so that a
+    // test or a measurement can tell that a frame really took that path (_fused.FRAME_STATS: fused_sort)
+    kFrameFusedSort = 1ll << 48;
 constexpr int kFrameCutGridShift = 16, kFrameBandSigShift = 32, kFrameCutoffsBufShift = 8;
 static_assert(kInfoPairs == 0 && kInfoXL == 4 && kInfoNeed == 5 && kInfoOnGrid == 6 && kInfoFlags == 7 && kInfoVerdict == 8,
               "size record: the header and the Python layer index these words by number");
@@ -134,6 +138,8 @@ static_assert(kFrameSpeculated == 1 && kFrameExact == 4 && kFrameSplit == 8 && k
                   kFrameFronts == 512 && kFrameBandCulled == 2048 && kFrameCleanupDeferred == 4096 && kFrameQuadLists == 8192 &&
                   kFrameRowsZeroed == 32768,
               "flag word: mojosplat_hip.h documents bits 2, 13 and 15, mojosplat_amd/*.py tests the others by value");
+static_assert(kFrameFusedSort == 281474976710656ll && (kFrameFusedSort & (kFrameCutSigMask | 0xffffll)) == 0,
+              "flag word: bit 48 lies above the cut-offs' signature; _fused.py counts fused_sort frames by this value");
 static_assert(((kFrameDepthCut | kFrameCutoffs | kFrameCutoffsBuf | kFrameCutSigMask) & 0x3f) == 0,
               "flag word: _fused.py withdraws the record's word for the cut-offs by keeping bits 0-5 alone");
 // word 5 as the device leaves it: bins the previous frame's clean-up redid because their sorted front was too short ...
@@ -197,6 +203,29 @@ struct LazyLists {
     // rasteriser -- enqueues them only if the word is set (rasterize_deferred_cleanup).
     int32_t *verdict;
 };
+// lazily sorted fronts: depth (entries) of a front, LDS room for it, depth buckets from the camera planes
+struct FrontParams {
+    uint32_t fixed_min;
+    int fixed_shift, front_k, front_cap;
+};
+// The sort of a frame whose rasteriser does it itself (rasterize.hip, k_sort_rasterize): what the merged sort launch
+// (binning.hip, k_tile_front<false, true>) would have been handed.  isect_emit_speculative fills it and launches the scatter
+// alone (taken = 1) when it would have launched the merged sort on 32-px bins at the default front depth; rasterize_fwd
+// then launches the fused kernel in place of its own.
+struct FusedSort {
+    int taken;              // out: the sort launch was left to the rasteriser
+    FrontParams fp;
+    const uint32_t *wg_depth;   // the scatter's per-workgroup depth ranges, n_wg pairs
+    int n_wg;
+    const int32_t *order;   // the band's bins, heaviest first, n_order of them: one workgroup each
+    int n_order;
+    uint32_t *tau_out;      // the next frame's cut-offs (or null), this frame's, the marks of its cut bins and their stamp
+    const uint32_t *tau_now, *has_far;
+    uint32_t cut_stamp;
+    int64_t cap;            // entries the key / id buffers hold (a bin beyond it: speculative overflow, left unsorted)
+    const uint64_t *keys;
+    int32_t *flatten_ids, *front_count;
+};
 // rasterize.hip: the clean-up launches a frame enqueued with lazy.verdict set left out, on `stream`; `key` = that pointer
 int rasterize_deferred_cleanup(const void *key, void *stream);
 int far_regen(const LazyLists &lazy, int tw, int n_tiles, int64_t cap, void *stream);
@@ -214,11 +243,6 @@ int project_bwd_from_rows(const Gaussians &g, const View &v, const int32_t *radi
 int check_pose_out(int64_t N, const float *out, const void *scratch, size_t scratch_bytes, const char *who);
 void isect_lazy_arrays(void *workspace, int64_t N, int tile_w, int tile_h, LazyLists *out);
 bool depth_cut_fits(int64_t N, int tile_w, int tile_h);
-// lazily sorted fronts: depth (entries) of a front, LDS room for it, depth buckets from the camera planes
-struct FrontParams {
-    uint32_t fixed_min;
-    int fixed_shift, front_k, front_cap;
-};
 FrontParams front_params(int tile_size, int lazy, float depth_near, float depth_far, bool merged, bool split);
 const int32_t *isect_order_array(const void *workspace, int64_t N, int tile_w, int tile_h);
 
@@ -239,7 +263,13 @@ int rasterize_fwd(int64_t N, int64_t M, int64_t density_hint, const float *means
                   // round 6: zero_bytes of memory every wave of the launch zeroes a slice of on its way (a differentiable frame's
                   // rows of raw gradient sums: the kernel is issue-bound and moves 70 MB in 90 us -- the 64 N bytes ride along
                   // instead of costing the backward a 10-us memset); null: nothing
-                  void *zero_mem = nullptr, size_t zero_bytes = 0);
+                  void *zero_mem = nullptr, size_t zero_bytes = 0,
+                  // non-null (taken != 0): the frame's sort launch was left to this call -- the fused kernel, k_sort_rasterize
+                  const FusedSort *fused = nullptr);
+// rasterize.hip: would rasterize_fwd take the frame's sort (the plain 3-channel kernel on ready-made records over a whole grid
+// of 32-px bins, two waves a block by its own rule -- or, `force`, whatever the rule says: tests on small images)?
+bool rasterize_takes_sort(int64_t density_hint, int CDIM, int W, int H, int tile_size, int tile_row_begin, int tile_row_end,
+                          const void *records, const int32_t *order, bool force);
 
 // rasterize_bwd.hip: ms_rasterize_to_pixels_3dgs_bwd with the forward frame's ready-made records (or null) and its
 // heaviest-first order of the image's tiles (16-px tiles only; or null: the kernel's own counting sort)
@@ -301,7 +331,9 @@ int isect_emit_speculative(int64_t N, const float *means2d, const int32_t *radii
                            int tile_w, int tile_h, int row_begin, int row_end, void *workspace, size_t workspace_bytes,
                            const int32_t *tile_ranges, const int64_t *isect_info_dev, int64_t capacity,
                            const int64_t *prev_info_host, int tight, int lazy, float depth_near, float depth_far,
-                           uint64_t *sort_keys, int32_t *flatten_ids, const DeferredTotal *defer, void *stream);
+                           uint64_t *sort_keys, int32_t *flatten_ids, const DeferredTotal *defer, void *stream,
+                           // non-null: the caller's rasteriser can sort the bins itself (FusedSort: filled, taken = 1 if left to it)
+                           FusedSort *fuse = nullptr);
 int isect_emit_exact(int64_t N, const float *means2d, const int32_t *radii, const float *depths, int tile_size,
                      int tile_w, int tile_h, int row_begin, int row_end, void *workspace, size_t workspace_bytes,
                      const int32_t *tile_ranges, const int64_t *host_info, int tight, int lazy, float depth_near,

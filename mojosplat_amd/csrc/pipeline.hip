@@ -152,6 +152,31 @@ extern "C" int ms_config_depth_cut(int mode, long long min_pairs) {
     if (min_pairs >= 0) g_cut_min_pairs.store(min_pairs, std::memory_order_relaxed);
     return MS_OK;
 }
+// Sort + rasterise in one launch (rasterize.hip, k_sort_rasterize): mode 0 = never (the merged sort launch, then the rasteriser),
+// 1 = on whole frames of plain 32-px bins whose rasteriser runs two waves a block by its own rule (the default), 2 = on every
+// such frame whatever that rule says (tests: small images).  Read ONCE from MOJOSPLAT_FUSED_SORT; ms_config_fused_sort changes
+// it in-process, like ms_config_depth_cut.
+namespace {
+std::atomic<int> g_fused_sort_mode{-1};
+void fused_sort_config_init() {
+    if (g_fused_sort_mode.load(std::memory_order_acquire) >= 0) return;
+    static std::atomic<int> once{0};
+    int expected = 0;
+    if (once.compare_exchange_strong(expected, 1)) {
+        const char *m = getenv("MOJOSPLAT_FUSED_SORT");
+        const int mode = m ? atoi(m) : 1;
+        g_fused_sort_mode.store(mode < 0 ? 0 : mode, std::memory_order_release);
+    } else {
+        while (g_fused_sort_mode.load(std::memory_order_acquire) < 0) {}
+    }
+}
+}  // namespace
+static int ms_fused_sort_mode() { fused_sort_config_init(); return g_fused_sort_mode.load(std::memory_order_relaxed); }
+extern "C" int ms_config_fused_sort(int mode) {
+    fused_sort_config_init();
+    if (mode >= 0) g_fused_sort_mode.store(mode, std::memory_order_relaxed);
+    return MS_OK;
+}
 // workgroups of the clean-up launch: 256, always.  (Rounds 1-2 launched ONE while recent frames had needed no clean-up;
 // measured in round 3, the frame costs the same with 1 ... 256 of them -- 0.1678-0.1681 ms at config 3: what costs is the
 // kernel boundary -- while the first frames that DO need the pass ran their hundreds of bins through one workgroup: 7-14 s
@@ -188,6 +213,19 @@ extern "C" int ms_render_workspace_layout(int64_t N, int tile_w, int tile_h, siz
     const WsLayout L = ws_layout(N, tile_w, tile_h);
     offsets[0] = L.off_means2d; offsets[1] = L.off_conics; offsets[2] = L.off_depths;
     offsets[3] = L.off_radii;   offsets[4] = L.off_ranges; offsets[5] = L.total;
+    return MS_OK;
+}
+
+// Where a frame's per-bin front counts (the length of a heavy bin's sorted front: binning.hip, k_tile_front) sit in its
+// workspace, in bytes: tile_w * tile_h int32 words.  For tests and measurements that compare the lists two settings leave.
+extern "C" int ms_render_front_count_offset(int64_t N, int tile_w, int tile_h, size_t *offset) {
+    MS_REQUIRE(offset && tile_w > 0 && tile_h > 0 && (int64_t)tile_w * tile_h < (1ll << 30) && N >= 0, MS_ERR_INVALID_ARG,
+               "render_front_count_offset: bad argument");
+    const WsLayout L = ws_layout(N, tile_w, tile_h);
+    char *base = reinterpret_cast<char *>((uintptr_t)1 << 20);   // (never dereferenced: only the arrays' places are asked for)
+    ms::LazyLists ll{};
+    ms::isect_lazy_arrays(base + L.off_isect, N, tile_w, tile_h, &ll);
+    *offset = (size_t)((const char *)ll.front_count - base);
     return MS_OK;
 }
 
@@ -450,11 +488,23 @@ static int render_fwd_impl(const ms_scene *prepared, int restart, const ms::Gaus
                 flags = ms::kFrameSpeculated | ms::kFrameSplit | base_flags;
                 if (phase == MS_RENDER_BEGIN) return MS_OK;
             } else {
+            // The sort rides in the rasteriser (rasterize.hip, k_sort_rasterize) where both would give a bin 512 threads: a whole
+            // frame of plain 32-px bins at the default front depth whose rasteriser is the plain 3-channel kernel on ready-made
+            // records with two waves a block.  A depth-cut frame qualifies like any other (the fused kernel keeps the sort launch's
+            // cut-off rules, the rasteriser's own are untouched); bands, differentiable frames, light-bet frames, deeper front
+            // levels and full-sort lanes keep the two launches.
+            ms::FusedSort fuse{};
+            const int fuse_mode = ms_fused_sort_mode();
+            const bool ask_fuse = fuse_mode != 0 && lazy == 1 && !bet_light && !aux_frame && !list_nq && !zero_rows && clip0 < 0 &&
+                                  ms_merged_sort_enabled() &&
+                                  ms::rasterize_takes_sort(prev_pairs > 0 ? prev_pairs : c, g.CDIM, v.W, v.H, f.tile_size, r0, r1, records,
+                                                           order, fuse_mode >= 2);
             if (int rc = ms::isect_emit_speculative(g.N, means2d, radii, depths, f.tile_size, tw, th, r0, r1,
                                                     ws + L.off_isect, L.isect_bytes, ranges, info, c, prev,
                                                     /*tight=*/(g.opacities != nullptr ? 1 : 0) | cull | claim_bit,
                                                     lazy | (bet_light ? 8 : 0) | (leaves_cutoffs ? 32 | (cut_out << 4) : 0),
-                                                    v.near_plane, v.far_plane, keys, ids, deferred ? &defer : nullptr, stream))
+                                                    v.near_plane, v.far_plane, keys, ids, deferred ? &defer : nullptr, stream,
+                                                    ask_fuse ? &fuse : nullptr))
                 return rc;
             mark(2);
             MS_HP_T(hp_t5);
@@ -489,9 +539,9 @@ static int render_fwd_impl(const ms_scene *prepared, int restart, const ms::Gaus
                                            lazy && !bet_light ? &lazy_lists : nullptr,
                                            records, order, clip0, clip1, f.stage_events ? f.stage_events[3] : nullptr, stream,
                                            list_nq ? (int32_t *)((char *)ids + ms::align_up((size_t)c * 4, 256)) : nullptr, quad_counts,
-                                           zero_rows, zero_rows_bytes))
+                                           zero_rows, zero_rows_bytes, fuse.taken ? &fuse : nullptr))
                 return rc;
-            flags = ms::kFrameSpeculated | (prev[ms::kInfoLarge] > 0 ? ms::kFrameLargeSorted : 0) | (no_split ? ms::kFrameNoSplit : 0) |
+            flags = (fuse.taken ? ms::kFrameFusedSort : 0) | ms::kFrameSpeculated | (prev[ms::kInfoLarge] > 0 ? ms::kFrameLargeSorted : 0) | (no_split ? ms::kFrameNoSplit : 0) |
                     (bet_light ? ms::kFrameLightBet : 0) | cut_bits | (lazy && !bet_light ? ms::kFrameFronts : 0) |
                     (lazy ? ms::kFrameLazy : 0) | base_flags | (lazy_lists.verdict ? ms::kFrameCleanupDeferred : 0) |
                     (zero_rows && r1 > r0 ? ms::kFrameRowsZeroed : 0) | (list_nq ? ms::kFrameQuadLists : 0);
@@ -547,7 +597,7 @@ static int render_fwd_impl(const ms_scene *prepared, int restart, const ms::Gaus
     host[ms::kInfoNeed] = (int64_t)need;
     const bool fronts = !split && lazy && ms::heavy(host) > 0;
     // the lists the caller may read back are in the EXACT layout (below)
-    flags = (flags & ~(ms::kFrameQuadLists | ms::kFrameFronts | ms::kFrameLazy)) | ms::kFrameExact | (list_nq ? ms::kFrameQuadLists : 0) |
+    flags = (flags & ~(ms::kFrameQuadLists | ms::kFrameFronts | ms::kFrameLazy | ms::kFrameFusedSort)) | ms::kFrameExact | (list_nq ? ms::kFrameQuadLists : 0) |
             (fronts ? ms::kFrameFronts : 0) | (lazy ? ms::kFrameLazy : 0);
     MS_REQUIRE(f.isect_buf && f.isect_bytes >= need, MS_ERR_WORKSPACE,
                "render_fwd: intersection buffer %zu < %zu (grow it and call again with resume=1)", f.isect_bytes,

@@ -53,6 +53,7 @@
 #include <vector>
 
 #include "ms_common.hpp"
+#include "sort_device.hpp"   // the fused kernel (k_sort_rasterize) sorts a bin's list with the binning stage's own routines
 
 namespace {
 
@@ -212,10 +213,13 @@ __device__ __forceinline__ bool raster_block_in_band(const RasterArgs &A, const 
 
 // One wave's share of a 16x16 block: NQ quads of block `sub` of tile `tile`, starting at quad part * NQ.  s_q: the
 // wave's NQ staging blocks.
-template <int CP, typename ColorT, bool AUX, int NQ, bool PACKED, bool LISTS = false>
+// LDS_IDS (k_sort_rasterize): the workgroup has just sorted the list itself -- its first s_len ids sit in s_ids (LDS), and
+// that is where the walk ends: neither the front count nor an id is read from memory.
+template <int CP, typename ColorT, bool AUX, int NQ, bool PACKED, bool LISTS = false, bool LDS_IDS = false>
 __device__ __forceinline__ void raster_tile(const RasterArgs &A, const int tile, const int sub, const int part,
                                             RasterStage<CP, AUX> *s_q, const int diag_slot,
-                                            float4 &r_a, float4 &r_b, float4 &r_c, int &r_g) {
+                                            float4 &r_a, float4 &r_b, float4 &r_c, int &r_g,
+                                            const int32_t *s_ids = nullptr, const int s_len = 0) {
     static_assert(!LISTS || (PACKED && !AUX), "quad lists: the plain 3-channel kernel on ready-made records");
     static_assert(!PACKED || CP == 3, "ready-made records carry three channels");
     using Stage = RasterStage<CP, AUX>;
@@ -254,7 +258,11 @@ __device__ __forceinline__ void raster_tile(const RasterArgs &A, const int tile,
     }
 
     int start, end, end_all;
-    raster_list_bounds(A, tile, start, end, end_all);
+    if constexpr (LDS_IDS) {
+        end_all = min(A.tile_ranges[2 * tile + 1], A.max_isects);
+        start = min(A.tile_ranges[2 * tile], end_all);
+        end = start + s_len;
+    } else raster_list_bounds(A, tile, start, end, end_all);
     const ColorT *colors = reinterpret_cast<const ColorT *>(A.colors);
     const float fbx = (float)bx + 0.5f, fby = (float)by + 0.5f;
     // (here rather than at the kernel's first line: s_setreg is a scheduling barrier, and up there it cost the
@@ -285,7 +293,8 @@ __device__ __forceinline__ void raster_tile(const RasterArgs &A, const int tile,
     }
     auto fetch_id = [&](int b0) {
         const int idx = b0 + lane;
-        r_g = idx < end ? A.flatten_ids[idx] : 0;
+        if constexpr (LDS_IDS) r_g = idx < end ? s_ids[idx - start] : 0;
+        else r_g = idx < end ? A.flatten_ids[idx] : 0;
     };
     auto gather = [&](int b0) {
         const int idx = b0 + lane;
@@ -653,6 +662,114 @@ __global__ __launch_bounds__(64, (CP <= 4 ? (NQ == 2 ? MS_RASTER_MINW2 : AUX ? M
     int tile, sub, part, slot;
     if (!raster_map_block<NQ>(A, (int)blockIdx.x, tile, sub, part, slot)) return;
     raster_tile<CP, ColorT, AUX, NQ, PACKED, LISTS>(A, tile, sub, part, s_stage, slot, r_a, r_b, r_c, r_g);
+}
+
+// ---- sort + rasterise in one launch (plain 32-px bins of a lazily sorted frame) ------------------------------------------
+// The merged sort launch (binning.hip, k_tile_front<false, true>) gives every bin one 512-thread workgroup; the rasteriser
+// with two waves a block gives the same bin 4 blocks x 2 waves = 512 threads.  Here ONE workgroup does both: all 512 threads
+// select and sort the bin's list as the sort launch does (the same two routines of sort_device.hpp, the same overflow guard,
+// front count and next-frame cut-off), the ids stay in LDS, one barrier, and wave w rasterises quads (w & 1) * 2 .. of block
+// w >> 1 with raster_tile as it is -- its ids come from LDS and the walk ends at the front the workgroup just computed.  No
+// workgroup waits on another: while one bin sits in its sort barriers the CU's other workgroups' waves have the vector pipe.
+// The sorted ids still go to flatten_ids (stores nobody waits for): the clean-up launches and the caller's read-back find
+// what they found.  LDS: the eight waves' staging blocks alias the sort's scratch (keys, bucket counters, reduction words);
+// only the ids live through both phases -- 38 144 + 8 192 B a workgroup, three workgroups a CU.
+constexpr int kFusedThreads = 512, kFusedCap = 2048;   // threads (= the sort launch's), ids of LDS room (= its front_cap)
+constexpr size_t kFusedSortLds = (size_t)kFusedCap * 8 + (size_t)kFrontNB * 4 + 64 * 4 + 16;   // (k_tile_front's layout)
+static_assert(SortCfg<kFusedThreads, kFrontK / kFusedThreads>::LDS <= kFusedSortLds, "a short list's whole sort fits the front's scratch");
+
+template <int CP, typename ColorT, bool PACKED>
+__global__ __launch_bounds__(kFusedThreads, 6) void k_sort_rasterize(RasterArgs A, ms::FusedSort S) {
+    using Stage = RasterStage<CP, false>;
+    constexpr int NW = kFusedThreads / 64;
+    constexpr size_t kScratch = sizeof(Stage) * 2 * NW > kFusedSortLds ? sizeof(Stage) * 2 * NW : kFusedSortLds;
+    static_assert(kScratch + kFusedCap * 4 <= 53 * 1024, "three workgroups a CU");
+    __shared__ __attribute__((aligned(16))) unsigned char s_scratch[kScratch];
+    __shared__ int32_t s_ids[kFusedCap];
+    if ((int)blockIdx.x >= S.n_order) return;
+    MS_DIAG_ONLY(const unsigned long long diag_wg0 = __builtin_amdgcn_s_memrealtime();)
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    // (the sort phase at raised priority: its few instructions between barriers go ahead of the resident rasterising waves,
+    // and the workgroup reaches its own VALU-bound phase sooner -- 158.8 / 158.9 us a frame against 159.3 / 160.3 at config 3)
+    __builtin_amdgcn_s_setprio(3);
+    const int tile = S.order[blockIdx.x];
+    int len = 0;   // sorted ids in s_ids (uniform)
+    {
+        const int start = A.tile_ranges[2 * tile], n = A.tile_ranges[2 * tile + 1] - start;
+        uint64_t *s_out = reinterpret_cast<uint64_t *>(s_scratch);
+        // (k_tile_front's rule for the next frame's cut-off of a bin whose list was sorted whole)
+        auto next_cut_whole = [&]() {
+            if (S.tau_out) S.tau_out[tile] = (S.cut_stamp && S.has_far[tile] == S.cut_stamp) ? S.tau_now[tile] : 0xffffffffu;
+        };
+        const bool fits = (int64_t)start + n <= S.cap;   // beyond cap: speculative overflow, the frame is redone (uniform)
+        if (n <= kFrontK) {   // a short list: sorted whole
+            if (n > 0 && fits) {
+                sort_segment_lds<kFusedThreads, kFrontK / kFusedThreads>(s_scratch, S.keys, start, n, tile, nullptr, nullptr, nullptr);
+                len = n;
+            }
+            if (tid == 0) next_cut_whole();
+        } else if (fits) {
+            uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_out + kFusedCap);
+            uint32_t *s_red = s_cnt + kFrontNB;
+            int *s_sel = reinterpret_cast<int *>(s_red + 64);
+            // the frame's own depth range (per-workgroup min / max left by the scatter) beats the camera planes
+            uint32_t fixed_min = S.fp.fixed_min;
+            int fixed_shift = S.fp.fixed_shift;
+            if (S.wg_depth) {
+                uint32_t lo = 0xffffffffu, hi = 0u;
+                for (int j = tid; j < S.n_wg; j += kFusedThreads) {
+                    lo = min(lo, S.wg_depth[2 * j]);
+                    hi = max(hi, S.wg_depth[2 * j + 1]);
+                }
+#pragma unroll
+                for (int d = 32; d > 0; d >>= 1) {
+                    lo = min(lo, (uint32_t)__shfl_xor((int)lo, d));
+                    hi = max(hi, (uint32_t)__shfl_xor((int)hi, d));
+                }
+                if (lane == 0) { s_red[w] = lo; s_red[16 + w] = hi; }
+                __syncthreads();
+#pragma unroll
+                for (int ww = 0; ww < NW; ++ww) { lo = min(lo, s_red[ww]); hi = max(hi, s_red[16 + ww]); }
+                __syncthreads();
+                if (hi >= lo) {
+                    const uint32_t span = hi - lo;
+                    const int bits = span ? 32 - __clz(span) : 0;
+                    fixed_min = lo;
+                    fixed_shift = max(0, bits - kFrontLogNB);
+                }
+            }
+            len = front_select_lds<kFusedThreads, 4>(S.keys + start, n, s_out, s_cnt, s_red, s_sel, fixed_min, fixed_shift,
+                                                     S.fp.front_k, min(S.fp.front_cap, kFusedCap));
+            if (tid == 0) {
+                S.front_count[tile] = len;
+                if (S.tau_out) {
+                    if (len >= n) next_cut_whole();
+                    else {   // (k_tile_front's margin: 2^19 steps of the float's bits beyond the bucket that completed the front)
+                        const unsigned long long cut = (unsigned long long)(uint32_t)s_sel[2] + (1ull << 19);
+                        S.tau_out[tile] = (uint32_t)(cut > 0xffffffffull ? 0xffffffffull : cut);
+                    }
+                }
+            }
+        }
+        for (int i = tid; i < len; i += kFusedThreads) {
+            const int32_t id = (int32_t)(uint32_t)s_out[i];
+            s_ids[i] = id;
+            S.flatten_ids[start + i] = id;
+        }
+    }
+    __syncthreads();   // the ids are in place and the sort's scratch is free: from here on the waves are on their own
+    __builtin_amdgcn_s_setprio(0);
+    MS_DIAG_ONLY(const unsigned long long diag_wg1 = __builtin_amdgcn_s_memrealtime();)
+    float4 r_a = make_float4(0.f, 0.f, 0.f, 0.f), r_b = r_a, r_c = r_a;
+    int r_g = 0;
+    const int slot = (int)blockIdx.x * NW + w;
+#ifdef MS_DIAG
+    // (the workgroup's start and its "sort done" time beside the wave's own stamps: scripts/raster_waves.py splits a
+    // workgroup's life into sort and rasterise)
+    if (g_diag_stamps && lane == 0) { g_diag_stamps[8 * (size_t)slot + 6] = diag_wg0; g_diag_stamps[8 * (size_t)slot + 7] = diag_wg1; }
+#endif
+    raster_tile<CP, ColorT, false, 2, PACKED, false, true>(A, tile, w >> 1, w & 1, reinterpret_cast<Stage *>(s_scratch) + 2 * w, slot,
+                                                            r_a, r_b, r_c, r_g, s_ids, len);
 }
 
 // ---- clean-up pass of a lazily sorted frame -----------------------------------------------------
@@ -1295,7 +1412,7 @@ void stash_cleanup(const RasterArgs &A, void (*launch)(const RasterArgs &, hipSt
 }
 
 template <int CP, typename ColorT>
-void launch_cp(const RasterArgs &A_in, hipStream_t stream, void *after_raster_event) {
+void launch_cp(const RasterArgs &A_in, hipStream_t stream, void *after_raster_event, const ms::FusedSort *fused) {
     RasterArgs A = A_in;
     A.zero_mem = nullptr; A.zero_per_wave = 0; A.zero_total = 0;
     const bool aux = A.last_ids != nullptr;   // (the per-entry index bookkeeping; render_alphas alone costs the plain kernel one store)
@@ -1314,6 +1431,9 @@ void launch_cp(const RasterArgs &A_in, hipStream_t stream, void *after_raster_ev
         else MS_LAUNCH_RASTER(AUXV, 4, PK);                    \
     } while (0)
     if constexpr (CP == 3) {
+        if (fused) {   // (rasterize_fwd has checked: ready-made records, two waves a block, neither per-pixel records nor quad lists)
+            hipLaunchKernelGGL((k_sort_rasterize<3, ColorT, true>), dim3((unsigned)fused->n_order), dim3(kFusedThreads), 0, stream, A, *fused);
+        } else
         if (A.records) {
             if (aux) MS_LAUNCH_RASTER_NQ(true, true);
             else if (A.quad_lists) {   // a differentiable frame that leaves its quads' lists for the backward
@@ -1344,12 +1464,12 @@ void launch_cp(const RasterArgs &A_in, hipStream_t stream, void *after_raster_ev
 }
 
 template <typename ColorT>
-int launch_fwd(const RasterArgs &A, hipStream_t stream, void *after_raster_event) {
-    if (A.cdim == 3) launch_cp<3, ColorT>(A, stream, after_raster_event);
-    else if (A.cdim <= 4) launch_cp<4, ColorT>(A, stream, after_raster_event);
-    else if (A.cdim <= 8) launch_cp<8, ColorT>(A, stream, after_raster_event);
-    else if (A.cdim <= 16) launch_cp<16, ColorT>(A, stream, after_raster_event);
-    else launch_cp<32, ColorT>(A, stream, after_raster_event);
+int launch_fwd(const RasterArgs &A, hipStream_t stream, void *after_raster_event, const ms::FusedSort *fused = nullptr) {
+    if (A.cdim == 3) launch_cp<3, ColorT>(A, stream, after_raster_event, fused);
+    else if (A.cdim <= 4) launch_cp<4, ColorT>(A, stream, after_raster_event, nullptr);
+    else if (A.cdim <= 8) launch_cp<8, ColorT>(A, stream, after_raster_event, nullptr);
+    else if (A.cdim <= 16) launch_cp<16, ColorT>(A, stream, after_raster_event, nullptr);
+    else launch_cp<32, ColorT>(A, stream, after_raster_event, nullptr);
     MS_LAUNCH_CHECK();
     return MS_OK;
 }
@@ -1385,6 +1505,8 @@ namespace {
 // only pays while staging is cheap against blending: with ready-made records (three 16-byte gathers
 // per entry, no arithmetic) every quad gets its own wave; staging from the per-stage arrays (seven
 // gathers + the folding arithmetic) 4 waves up to 150 entries per block, 2 up to 1 500, else 1.
+// (the block counts from which choose_parts looks at a plain forward frame's density: a whole 1080p frame on 32-px bins, 4K on 64)
+bool plain_bins(int tile_size, int64_t blocks) { return (tile_size == 32 && blocks >= 8000) || (tile_size == 64 && blocks >= 16384); }
 int choose_parts(int64_t blocks, int64_t density_hint, bool records, bool plain32 = false) {
     if (const int forced = raster_parts_override()) return forced;
     // (plain forward frames on 32- / 64-px bins whose size record counts 150-600 pairs per 16x16 block -- config 3: 241,
@@ -1411,7 +1533,8 @@ int ms::rasterize_fwd(int64_t N, int64_t M, int64_t density_hint, const float *m
                       float *render_colors, float *render_alphas, int32_t *last_ids,
                       const ms::LazyLists *lazy, const void *records, const int32_t *order, int clip_row16_begin,
                       int clip_row16_end, void *after_raster_event, void *stream, int32_t *quad_lists, int32_t *quad_counts,
-                      void *zero_mem, size_t zero_bytes) {
+                      void *zero_mem, size_t zero_bytes, const ms::FusedSort *fused) {
+    if (fused && !fused->taken) fused = nullptr;
     MS_REQUIRE(N >= 0 && M >= 0 && M <= 0x7fffffffll, MS_ERR_INVALID_ARG, "rasterize_fwd: bad N/M");
     MS_REQUIRE(!zero_mem || (((uintptr_t)zero_mem & 15) == 0 && (zero_bytes & 15) == 0), MS_ERR_INVALID_ARG,
                "rasterize_fwd: the memory to zero must be 16-byte aligned and a multiple of 16 bytes");
@@ -1458,15 +1581,31 @@ int ms::rasterize_fwd(int64_t N, int64_t M, int64_t density_hint, const float *m
     }
     const int64_t blocks = (int64_t)band_tiles * A.nsub;
     MS_REQUIRE(blocks <= 0x7fffffff, MS_ERR_TOO_LARGE, "rasterize_fwd: too many tiles");
-    A.parts = choose_parts(blocks, density_hint, A.records != nullptr, ((tile_size == 32 && blocks >= 8000) || (tile_size == 64 && blocks >= 16384)) && !last_ids && lazy != nullptr);
+    A.parts = choose_parts(blocks, density_hint, A.records != nullptr, plain_bins(tile_size, blocks) && !last_ids && lazy != nullptr);
+    if (fused) {
+        // the frame's sort was left to this launch: the caller asked rasterize_takes_sort first, and the rest is what it could not see
+        MS_REQUIRE(A.records && lazy && lazy->front_count && lazy->front_threshold == kFrontK && order && !last_ids && !A.quad_lists &&
+                       !zero_mem && tile_size == 32 && fused->n_order == band_tiles && fused->fp.front_cap <= kFusedCap && M == fused->cap,
+                   MS_ERR_INVALID_ARG, "rasterize_fwd: this frame cannot sort its bins in the rasteriser");
+        A.parts = 2;
+    }
     A.nblocks = (int)blocks;
     A.ngrid = (int)blocks;
     if (order) A.ngrid = ((band_tiles + 7) / 8) * 8 * A.nsub;   // tiles dealt over the 8 XCDs, each with its nsub blocks
     A.max_isects = (int)M;
     MS_REQUIRE(N > 0 || M == 0, MS_ERR_INVALID_ARG, "rasterize_fwd: M > 0 with N == 0");
     A.n_gauss = (int)(N < 0x7fffffffll ? (N > 0 ? N : 1) : 0x7fffffffll);
-    if (color_dtype == MS_COLOR_F16) return launch_fwd<__half>(A, (hipStream_t)stream, after_raster_event);
-    return launch_fwd<float>(A, (hipStream_t)stream, after_raster_event);
+    if (color_dtype == MS_COLOR_F16) return launch_fwd<__half>(A, (hipStream_t)stream, after_raster_event, fused);
+    return launch_fwd<float>(A, (hipStream_t)stream, after_raster_event, fused);
+}
+
+bool ms::rasterize_takes_sort(int64_t density_hint, int CDIM, int W, int H, int tile_size, int tile_row_begin, int tile_row_end,
+                              const void *records, const int32_t *order, bool force) {
+    if (CDIM != 3 || !records || ((uintptr_t)records & 15) != 0 || !order || tile_size != 32 || W <= 0 || H <= 0) return false;
+    const int tw = (W + 31) / 32, th = (H + 31) / 32;
+    if (tile_row_begin != 0 || tile_row_end != th) return false;   // (a band keeps the two launches)
+    const int64_t blocks = (int64_t)tw * th * 4;
+    return force || choose_parts(blocks, density_hint, true, plain_bins(tile_size, blocks)) == 2;
 }
 
 #ifdef MS_DIAG

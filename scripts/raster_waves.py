@@ -1,4 +1,4 @@
-"""Per-wave picture of k_rasterize_fwd on a BASELINE config (diagnostic build, -DMS_DIAG):
+"""Per-wave picture of k_rasterize_fwd (or the fused k_sort_rasterize) on a BASELINE config (diagnostic build, -DMS_DIAG):
 when each wave started and ended (shader clock), how many (quad, entry) evaluations and batches it ran.
 
     python -m mojosplat_amd.csrc.build --diag
@@ -53,6 +53,7 @@ def main():
     torch.cuda.synchronize()
     _hip.check(L.ms_diag_set_stamps(None), "diag")
     d = buf.cpu().numpy().reshape(-1, 8)
+    slots = np.nonzero(d[:, 1] != 0)[0]
     d = d[d[:, 1] != 0]
     t0, t1 = d[:, 0].astype(np.float64), d[:, 1].astype(np.float64)
     evals, batches = (d[:, 2] & 0xffffffff).astype(np.float64), (d[:, 2] >> 32).astype(np.float64)
@@ -98,6 +99,25 @@ def main():
         if one.any():
             out["one_batch_wave_life_cycles_p50"] = float(np.median(cyc[one]))
             out["one_batch_startup_cycles_p50"] = float(np.median(first[one]))
+    # round 7: a workgroup of the fused kernel (k_sort_rasterize: eight waves, slots 8 b .. 8 b + 7) stamps its start and its
+    # "sort done" time beside its waves' own stamps -- a workgroup's life split into sort and rasterise, and what its waves
+    # hold while they wait: `resident` counts a wave from the workgroup's start to its own end, `held` to the workgroup's end
+    # (its LDS, and with it the room for the next workgroup, is only given back then)
+    wg0, wg1 = d[:, 6].astype(np.float64), d[:, 7].astype(np.float64)
+    if (wg1 > 0).all() and len(d):
+        wg = slots // 8
+        wg_end = np.zeros(int(wg.max()) + 1)
+        np.maximum.at(wg_end, wg, t1)
+        held_end = wg_end[wg]
+        kspan = t1.max() - wg0.min()
+        out["fused"] = {"workgroups": int(len(np.unique(wg))), "kernel_us": float(kspan) / 100.0,
+                        "sort_share_of_workgroup_life": float((wg1 - wg0).sum() / np.maximum(held_end - wg0, 1.0).sum()),
+                        "sort_us": {k: float(np.percentile(wg1 - wg0, q)) / 100.0 for k, q in (("p10", 10), ("p50", 50), ("p90", 90), ("max", 100))},
+                        "workgroup_life_us": {k: float(np.percentile(held_end - wg0, q)) / 100.0 for k, q in (("p10", 10), ("p50", 50), ("p90", 90), ("max", 100))},
+                        "mean_resident_waves": float((t1 - wg0).sum() / kspan), "mean_held_wave_slots": float((held_end - wg0).sum() / kspan),
+                        "mean_rasterising_waves": float((t1 - t0).sum() / kspan),
+                        "waves_in_sort_at_percent_of_kernel": {str(p): int(((wg0 <= t) & (wg1 > t)).sum()) for p in (0, 2, 5, 10, 20, 40, 60, 80, 95)
+                                                               for t in [wg0.min() + kspan * p / 100.0]}}
     out["xcc_wave_counts"] = np.bincount(xcc, minlength=8).tolist()
     out["xcc_end_percent"] = [float((t1[xcc == x].max() - base) / span * 100) if (xcc == x).any() else None for x in range(8)]
     print(json.dumps(out))
