@@ -72,7 +72,7 @@ extern "C" {
 
 #define MS_ABI_VERSION 5   /* 2: ms_render_bwd takes the frame's image (render_colors); 3: ms_render_redo_counts, the band-frame pair, ms_scene_prepare;
                               4: the pose-gradient entry points (ms_pose_scratch_bytes, ms_*_pose); 5: ms_adam_step
-                              (the ms_densify_*, ms_mcmc_*, ms_knn* and ms_ply_* entry points, ms_config_fused_sort, ms_render_front_count_offset and bit 48
+                              (the ms_densify_*, ms_mcmc_*, ms_knn* and ms_ply_* entry points, ms_config_fused_sort, ms_render_front_count_offset and bits 48 and 49
                               of the flag word were added under 5: new symbols and a new bit, nothing existing changed) */
 
 typedef enum ms_status {
@@ -268,7 +268,10 @@ int ms_project_gaussians_bwd(int64_t N, const float *means3d, const float *scale
 int ms_config_depth_cut(int mode, long long min_pairs);
 /* Sort + rasterise in one launch (whole forward frames on plain 32-px bins): mode 0 never / 1 where the rasteriser runs two
  * waves a block by its own rule (default) / 2 on every such frame; < 0 leaves it.  MOJOSPLAT_FUSED_SORT in the environment is
- * read once; this changes the setting in-process.  The image is the same whatever the mode. */
+ * read once; this changes the setting in-process.  The image is the same whatever the mode.  Bit 2 of the mode (1 | 4, 2 | 4)
+ * keeps the clean-up launch behind such a frame: without it a bin whose sorted front runs out with pixels alive fetches the rest
+ * of its list in the same workgroup, nothing is launched behind the rasteriser and bit 49 of word 7 of host_info says so
+ * (never on a depth-cut frame, which keeps its clean-up launches). */
 int ms_config_fused_sort(int mode);
 
 /* ms_render_bwd in two halves, for a multi-GPU rank's differentiable BAND frame (a 3-channel frame at a tile size that is a

@@ -139,6 +139,7 @@ def _grow(st, key, nbytes, dev, slack=1.0):
 #   depth_cut         frames that dropped the pairs behind their bins' depth cut-offs
 #   regen_mismatch    frames whose clean-up launches brought back a pair the count kernel had not counted (a bug if ever > 0)
 #   fused_sort        frames whose bins were sorted by the workgroups that rasterised them (one launch for both)
+#   cleanup_in_kernel ... of those, the frames whose bins finish their own short fronts: no clean-up launch was enqueued
 #   front_level_up / full_sort_on   the lane's lazy-sorting mode escalated
 #   lazy_sort_retry   a lane on full sorts tried lazily sorted fronts again
 FRAME_STATS = None
@@ -176,6 +177,8 @@ def _count_frame(stats, frame, host, grew, counts_valid=True):
         stats["depth_cut"] = stats.get("depth_cut", 0) + 1
     if (flags & 281474976710656) and not (flags & 4):   # bit 48: the sort launch rode in the rasteriser (k_sort_rasterize)
         stats["fused_sort"] = stats.get("fused_sort", 0) + 1
+        if flags & 562949953421312:   # bit 49: ... and its bins finish their own short fronts, no clean-up launch behind it
+            stats["cleanup_in_kernel"] = stats.get("cleanup_in_kernel", 0) + 1
     if (flags & 4096) and not (flags & 4):   # the band pair left the clean-up launches to its finishing half (_band.py)
         stats["cleanup_deferred"] = stats.get("cleanup_deferred", 0) + 1
         if len(host) > 8 and int(host[8]) != 0:   # ... which found the rasteriser asking for them

@@ -363,6 +363,8 @@ def config_depth_cut(mode=None, min_pairs=None):
 def config_fused_sort(mode=None):
     """Sort + rasterise in one launch (include/mojosplat_hip.h, ms_config_fused_sort): mode 0 never / 1 where the
     rasteriser runs two waves a block by its own rule (the default) / 2 on every whole frame of plain 32-px bins.
+    Adding 4 to mode 1 or 2 keeps the clean-up launch behind such a frame; without it the bins of a fused frame that
+    has no depth cut finish their own short fronts in the kernel (bit 49 of the frame's flag word) and nothing follows it.
     Process-wide; None leaves it alone.  The library reads MOJOSPLAT_FUSED_SORT once -- tests and measurements that
     switch inside one process call this instead of writing os.environ."""
     check(lib().ms_config_fused_sort(-1 if mode is None else int(mode)), "ms_config_fused_sort")

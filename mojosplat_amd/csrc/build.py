@@ -33,6 +33,38 @@ def _stale() -> bool:
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 
+# k_sort_rasterize (rasterize.hip) keeps six waves a SIMD and three workgroups a CU only inside these figures, and it stays
+# inside them because its rarely taken code is kept out of its hot loop's registers by hand (empty asm statements): a compiler
+# that decides otherwise would bring scratch back silently.  `build --verbose` checks what the compiler reports.
+FUSED_KERNEL_LIMITS = {"VGPRs": 80, "ScratchSize [bytes/lane]": 0, "LDS Size [bytes/block]": 46336}
+
+
+def check_fused_kernel_resources(remarks: str) -> dict:
+    """-> {mangled name of each k_sort_rasterize instance: {figure: value}} from the compiler's resource remarks; raises
+    if a figure exceeds its limit, or if fewer than two instances (float and half colours) reported all three figures."""
+    import re
+    figure = re.compile(r"remark:.*?(%s): (\d+)" % "|".join(re.escape(k) for k in FUSED_KERNEL_LIMITS))
+    found, name = {}, None
+    for line in remarks.splitlines():
+        m = re.search(r"remark:.*Function Name: (\S+)", line)
+        if m:
+            name = m.group(1) if "k_sort_rasterize" in m.group(1) else None
+            if name:
+                found.setdefault(name, {})
+            continue
+        m = figure.search(line)
+        if m and name:
+            found[name][m.group(1)] = int(m.group(2))
+    whole = {n: f for n, f in found.items() if set(f) == set(FUSED_KERNEL_LIMITS)}
+    if len(whole) < 2:
+        raise RuntimeError(f"resource remarks of k_sort_rasterize: all of {sorted(FUSED_KERNEL_LIMITS)} for {len(whole)} instance(s), expected 2")
+    for n, f in whole.items():
+        for k, limit in FUSED_KERNEL_LIMITS.items():
+            if f[k] > limit:
+                raise RuntimeError(f"{n}: {k} = {f[k]}, over {limit}")
+    return whole
+
+
 def build(force: bool = False, verbose: bool = False, diag: bool = False) -> str:
     """diag=True builds libmojosplat_hip_diag.so with -DMS_DIAG (per-wave stamps in the rasteriser;
     scripts/raster_waves.py) next to the product library -- never loaded unless MOJOSPLAT_HIP_LIB names it."""
@@ -54,11 +86,22 @@ def build(force: bool = False, verbose: bool = False, diag: bool = False) -> str
         if verbose:
             cmd += ["-Rpass-analysis=kernel-resource-usage"]
             print(" ".join(cmd))
-        procs.append((src, subprocess.Popen(cmd)))
+        # (verbose: the rasteriser's remarks are kept, for the check of the fused kernel's figures below)
+        keep = verbose and os.path.basename(src) == "rasterize.hip"
+        procs.append((src, subprocess.Popen(cmd, stderr=subprocess.PIPE if keep else None, text=True if keep else None)))
         objs.append(obj)
-    failed = [s for s, p in procs if p.wait() != 0]
+    remarks = ""
+    failed = []
+    for s, p in procs:
+        if p.stderr is not None:
+            remarks = p.communicate()[1]
+            sys.stderr.write(remarks)
+        if p.wait() != 0:
+            failed.append(s)
     if failed:
         raise RuntimeError(f"hipcc failed for: {failed}")
+    if remarks:
+        check_fused_kernel_resources(remarks)
     cmd = [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", lib + ".tmp"] + objs
     subprocess.check_call(cmd)
     os.replace(lib + ".tmp", lib)

@@ -130,7 +130,11 @@ constexpr int64_t
     // bit 48: the frame's sort launch rode in its rasteriser (rasterize.hip, k_sort_rasterize): one workgroup per 32-px bin sorted
     // the bin's list and rasterised its four blocks.  Nothing downstream reads the lists differently -- the bit exists so that a
     // test or a measurement can tell that a frame really took that path (_fused.FRAME_STATS: fused_sort)
-    kFrameFusedSort = 1ll << 48;
+    kFrameFusedSort = 1ll << 48,
+    // bit 49 (only beside bit 48): this frame's bins finish their own short fronts -- a workgroup of the fused kernel whose
+    // sorted front ran out with pixels alive fetched the rest of its list itself; no clean-up launch was enqueued
+    // (_fused.FRAME_STATS: cleanup_in_kernel)
+    kFrameCleanupInKernel = 1ll << 49;
 constexpr int kFrameCutGridShift = 16, kFrameBandSigShift = 32, kFrameCutoffsBufShift = 8;
 static_assert(kInfoPairs == 0 && kInfoXL == 4 && kInfoNeed == 5 && kInfoOnGrid == 6 && kInfoFlags == 7 && kInfoVerdict == 8,
               "size record: the header and the Python layer index these words by number");
@@ -140,6 +144,8 @@ static_assert(kFrameSpeculated == 1 && kFrameExact == 4 && kFrameSplit == 8 && k
               "flag word: mojosplat_hip.h documents bits 2, 13 and 15, mojosplat_amd/*.py tests the others by value");
 static_assert(kFrameFusedSort == 281474976710656ll && (kFrameFusedSort & (kFrameCutSigMask | 0xffffll)) == 0,
               "flag word: bit 48 lies above the cut-offs' signature; _fused.py counts fused_sort frames by this value");
+static_assert(kFrameCleanupInKernel == 562949953421312ll && (kFrameCleanupInKernel & (kFrameFusedSort | kFrameCutSigMask | 0xffffll)) == 0,
+              "flag word: bit 49, next to the fused sort's; _fused.py counts cleanup_in_kernel frames by this value");
 static_assert(((kFrameDepthCut | kFrameCutoffs | kFrameCutoffsBuf | kFrameCutSigMask) & 0x3f) == 0,
               "flag word: _fused.py withdraws the record's word for the cut-offs by keeping bits 0-5 alone");
 // word 5 as the device leaves it: bins the previous frame's clean-up redid because their sorted front was too short ...
@@ -225,6 +231,8 @@ struct FusedSort {
     int64_t cap;            // entries the key / id buffers hold (a bin beyond it: speculative overflow, left unsorted)
     const uint64_t *keys;
     int32_t *flatten_ids, *front_count;
+    int finish_short;       // (set by the frame's caller behind `taken`) a bin whose front is shorter than its list walks on by
+                            // itself and rasterize_fwd enqueues no clean-up launch: never on a depth-cut frame (cut_stamp != 0)
 };
 // rasterize.hip: the clean-up launches a frame enqueued with lazy.verdict set left out, on `stream`; `key` = that pointer
 int rasterize_deferred_cleanup(const void *key, void *stream);

@@ -154,7 +154,9 @@ extern "C" int ms_config_depth_cut(int mode, long long min_pairs) {
 }
 // Sort + rasterise in one launch (rasterize.hip, k_sort_rasterize): mode 0 = never (the merged sort launch, then the rasteriser),
 // 1 = on whole frames of plain 32-px bins whose rasteriser runs two waves a block by its own rule (the default), 2 = on every
-// such frame whatever that rule says (tests: small images).  Read ONCE from MOJOSPLAT_FUSED_SORT; ms_config_fused_sort changes
+// such frame whatever that rule says (tests: small images).  Bit 2 (value 4, ORed onto 1 or 2) keeps the clean-up launch behind
+// a fused frame: without it the bins of a fused frame that has no depth cut finish their own short fronts and nothing is
+// launched behind the rasteriser (flag word bit 49).  Read ONCE from MOJOSPLAT_FUSED_SORT; ms_config_fused_sort changes
 // it in-process, like ms_config_depth_cut.
 namespace {
 std::atomic<int> g_fused_sort_mode{-1};
@@ -495,10 +497,10 @@ static int render_fwd_impl(const ms_scene *prepared, int restart, const ms::Gaus
             // levels and full-sort lanes keep the two launches.
             ms::FusedSort fuse{};
             const int fuse_mode = ms_fused_sort_mode();
-            const bool ask_fuse = fuse_mode != 0 && lazy == 1 && !bet_light && !aux_frame && !list_nq && !zero_rows && clip0 < 0 &&
+            const bool ask_fuse = (fuse_mode & 3) != 0 && lazy == 1 && !bet_light && !aux_frame && !list_nq && !zero_rows && clip0 < 0 &&
                                   ms_merged_sort_enabled() &&
                                   ms::rasterize_takes_sort(prev_pairs > 0 ? prev_pairs : c, g.CDIM, v.W, v.H, f.tile_size, r0, r1, records,
-                                                           order, fuse_mode >= 2);
+                                                           order, (fuse_mode & 3) >= 2);
             if (int rc = ms::isect_emit_speculative(g.N, means2d, radii, depths, f.tile_size, tw, th, r0, r1,
                                                     ws + L.off_isect, L.isect_bytes, ranges, info, c, prev,
                                                     /*tight=*/(g.opacities != nullptr ? 1 : 0) | cull | claim_bit,
@@ -532,6 +534,11 @@ static int render_fwd_impl(const ms_scene *prepared, int restart, const ms::Gaus
                     lazy_lists.verdict = (int32_t *)((int64_t *)mirror + ms::kInfoVerdict);
                 }
             }
+            // (a fused frame's bins finish their own short fronts unless the frame is depth-cut -- a bin may then be short of
+            // pairs that only the clean-up's regeneration brings back -- or the switch keeps the launch)
+            // (... or its clean-up is deferred to the finishing half of a band pair: that frame keeps the verdict word and the
+            // stashed launches exactly as they were, so that bit 12 never marks a frame that deferred nothing)
+            fuse.finish_short = fuse.taken && cut_stamp == 0u && fuse.cut_stamp == 0u && !(fuse_mode & 4) && !late_cleanup ? 1 : 0;
             if (int rc = ms::rasterize_fwd(g.N, c, prev_pairs > 0 ? prev_pairs : c, means2d, conics, g.colors, g.color_dtype, g.CDIM,
                                            g.opacities, f.backgrounds, v.W, v.H, f.tile_size, r0, r1, ranges, ids,
                                            f.render_colors, f.render_alphas, f.last_ids,
@@ -541,7 +548,7 @@ static int render_fwd_impl(const ms_scene *prepared, int restart, const ms::Gaus
                                            list_nq ? (int32_t *)((char *)ids + ms::align_up((size_t)c * 4, 256)) : nullptr, quad_counts,
                                            zero_rows, zero_rows_bytes, fuse.taken ? &fuse : nullptr))
                 return rc;
-            flags = (fuse.taken ? ms::kFrameFusedSort : 0) | ms::kFrameSpeculated | (prev[ms::kInfoLarge] > 0 ? ms::kFrameLargeSorted : 0) | (no_split ? ms::kFrameNoSplit : 0) |
+            flags = (fuse.taken ? ms::kFrameFusedSort : 0) | (fuse.taken && fuse.finish_short ? ms::kFrameCleanupInKernel : 0) | ms::kFrameSpeculated | (prev[ms::kInfoLarge] > 0 ? ms::kFrameLargeSorted : 0) | (no_split ? ms::kFrameNoSplit : 0) |
                     (bet_light ? ms::kFrameLightBet : 0) | cut_bits | (lazy && !bet_light ? ms::kFrameFronts : 0) |
                     (lazy ? ms::kFrameLazy : 0) | base_flags | (lazy_lists.verdict ? ms::kFrameCleanupDeferred : 0) |
                     (zero_rows && r1 > r0 ? ms::kFrameRowsZeroed : 0) | (list_nq ? ms::kFrameQuadLists : 0);

@@ -176,6 +176,60 @@ __device__ __forceinline__ void wave_lds_sync() {
 constexpr int kGroup = MS_RASTER_GROUP;   // records evaluated per trip of the blend loop
 constexpr int kUnroll = MS_RASTER_UNROLL; // trips unrolled
 
+// ---- the two pieces every walk OUTSIDE raster_tile's blend loop shares (the clean-up kernel k_tile_redo and the fused
+// kernel's bins that walk on behind their fronts): ONE spelling each, so that a change to the alpha clamp or the stop rule
+// cannot miss a copy.  (raster_tile keeps its own, interleaved with its staging and its two-record trips; the bit-for-bit
+// tests of the clean-up paths against the per-stage path hold the three together.)
+// Which of NQ quads of a 16x16 block -- quads qbase .. qbase + NQ - 1; fbx / fby: the block's first pixel centre -- the
+// alpha >= 1/255 ellipse of a ready-made record can reach: raster_tile's exact ellipse-vs-rectangle test (log2 units).
+template <int NQ>
+__device__ __forceinline__ int record_reach(const float4 &ra, const float4 &rb, const float4 &rc, const float fbx, const float fby,
+                                            const int qbase) {
+    constexpr float kInf = __builtin_huge_valf();
+    const float smax = rc.y, nb_c = rc.z, nb_a = rc.w;
+    if (smax == kInf) return (1 << NQ) - 1;   // not positive definite, or the 0.999 clamp can bind: no bound
+    int hit = 0;
+    if (smax > -kInf) {
+#pragma unroll
+        for (int qi = 0; qi < NQ; ++qi) {
+            const int qq = qbase + qi;
+            const float xl = fbx + (float)((qq & 1) * 8) - ra.x, xh = xl + 7.0f;
+            const float yl = fby + (float)((qq >> 1) * 8) - ra.y, yh = yl + 7.0f;
+            const bool in_x = xl <= 0.f && xh >= 0.f, in_y = yl <= 0.f && yh >= 0.f;
+            float best = (in_x && in_y) ? 0.f : 3.0e38f;
+            if (!in_x) {
+                const float ddx = xl > 0.f ? xl : xh;
+                const float ddy = fminf(fmaxf(nb_c * ddx, yl), yh);
+                best = -(ra.z * ddx * ddx + rb.x * ddy * ddy + ra.w * ddx * ddy);
+            }
+            if (!in_y) {
+                const float ddy = yl > 0.f ? yl : yh;
+                const float ddx = fminf(fmaxf(nb_a * ddy, xl), xh);
+                best = fminf(best, -(ra.z * ddx * ddx + rb.x * ddy * ddy + ra.w * ddx * ddy));
+            }
+            hit |= (best <= smax) ? (1 << qi) : 0;
+        }
+    }
+    return hit;
+}
+// One entry blended into one pixel with k_rasterize_fwd's generic (CHECK) arithmetic, operation for operation: the entry's
+// mean (mx, my), a', b', c' and log2(opacity); the pixel centre; the pixel's scaled transmittance T and flush multiplier kq
+// (both updated).  -> 255 * the blend weight (0 for a pixel that stops here or has stopped): the caller adds colour * it.
+__device__ __forceinline__ float blend_entry(const float mx, const float my, const float ca, const float cb, const float cc,
+                                             const float l2o, const float px, const float py, float &T, float &kq) {
+    const float dx = mx - px, dy = my - py;
+    const float la = fmaf(dx, fmaf(ca, dx, cb * dy), fmaf(cc * dy, dy, l2o));
+    float alpha = fminf(ms::kMaxAlpha, __builtin_amdgcn_exp2f(la));
+    alpha = la <= l2o ? alpha : 0.f;
+    const float mj = alpha * kq;
+    const float vj = mj * T;
+    const float nt = fmaf(vj, -ms::kAlphaOfV, T);
+    const bool dead = !(nt > ms::kTransmittanceStop * ms::kTScale);
+    kq = dead ? 0.f : kq;
+    T = dead ? T : nt;
+    return dead ? 0.f : vj;
+}
+
 // One LDS block per (wave, quad): the records of the entries that REACH the quad, compacted in list order.
 // The three arrays sit at fixed offsets, so a record's words share one index * 16 B and the blend loop
 // reaches kGroup consecutive records from ONE address register through the instructions' offset fields.
@@ -190,6 +244,8 @@ struct RasterStage {
     static constexpr int CS = (CP == 3) ? (AUX ? 2 : 1) : CP;
     static constexpr int kSlots = kBatch + kGroup;      // room for the neutral records that pad a list to a multiple of kGroup
     __attribute__((aligned(16))) float col[(kSlots * CS + 3) & ~3];  // CP == 3: blue (, index in batch)
+    // (the padding behind col[kSlots * CS - 1] is NOT free: k_sort_rasterize keeps the word its waves raise to ask for more
+    // of their bin's list in col[kSlots * CS + 1] of its last staging block -- nothing here may write beyond kSlots * CS)
     float4 a[kSlots];        // mean.x, mean.y, a', b'
     float4 b[kSlots];        // c', log2(opacity), (r, g | index in batch, -)
 };
@@ -215,11 +271,28 @@ __device__ __forceinline__ bool raster_block_in_band(const RasterArgs &A, const 
 // wave's NQ staging blocks.
 // LDS_IDS (k_sort_rasterize): the workgroup has just sorted the list itself -- its first s_len ids sit in s_ids (LDS), and
 // that is where the walk ends: neither the front count nor an id is read from memory.
-template <int CP, typename ColorT, bool AUX, int NQ, bool PACKED, bool LISTS = false, bool LDS_IDS = false>
+// ... and the walk can be RESUMED there (`more`, a RasterMore): in a launch whose bins finish their short fronts themselves
+// (more.finishes) no wave queues a bin for the clean-up launch, and a workgroup whose front is shorter than its list
+// (more.active, uniform over the workgroup) hands the caller's step its pixels' state when the ids have run out -- T, kq and
+// pix in the registers they live in, and whether the wave ran dry with a pixel still live.  The step holds workgroup barriers:
+// every wave of such a workgroup calls it, exactly once, after storing its pixels -- no wave leaves before.
+struct RasterNoMore {
+    bool finishes = false, active = false;
+    template <typename TT, typename PP>
+    __device__ __forceinline__ void walk_on(bool, TT &, TT &, PP &) const {}
+};
+template <typename Step>
+struct RasterMore {
+    bool finishes;   // the launch has no clean-up launch behind it (uniform over the launch)
+    bool active;     // this workgroup's front is shorter than its list and it may walk on (uniform over the workgroup)
+    Step walk_on;
+};
+template <int CP, typename ColorT, bool AUX, int NQ, bool PACKED, bool LISTS = false, bool LDS_IDS = false, typename More = RasterNoMore>
 __device__ __forceinline__ void raster_tile(const RasterArgs &A, const int tile, const int sub, const int part,
                                             RasterStage<CP, AUX> *s_q, const int diag_slot,
                                             float4 &r_a, float4 &r_b, float4 &r_c, int &r_g,
-                                            const int32_t *s_ids = nullptr, const int s_len = 0) {
+                                            const int32_t *s_ids = nullptr, const int s_len = 0, More more = More{}) {
+    static_assert(LDS_IDS || std::is_same<More, RasterNoMore>::value, "only a workgroup that sorted the list itself can fetch more of it");
     static_assert(!LISTS || (PACKED && !AUX), "quad lists: the plain 3-channel kernel on ready-made records");
     static_assert(!PACKED || CP == 3, "ready-made records carry three channels");
     using Stage = RasterStage<CP, AUX>;
@@ -228,7 +301,8 @@ __device__ __forceinline__ void raster_tile(const RasterArgs &A, const int tile,
     const int qbase = NQ == 4 ? 0 : part * NQ;
     const int tile_y = tile / A.tw, tile_x = tile - tile_y * A.tw;
     const int sub_y = sub / A.nsx, sub_x = sub - sub_y * A.nsx;
-    if (!raster_block_in_band(A, tile, sub)) {   // a band cut at 16-px rows inside coarser tiles: blocks outside it are not this call's
+    // (LDS_IDS: a whole frame, never a band -- and no wave may leave a workgroup that holds barriers further down)
+    if (!LDS_IDS && !raster_block_in_band(A, tile, sub)) {   // a band cut at 16-px rows inside coarser tiles: blocks outside it are not this call's
         if constexpr (LISTS) {   // (nothing of this block is rendered: its quads leave empty lists)
             if ((threadIdx.x & 63) < NQ) A.quad_counts[(size_t)tile * A.quad_nq + sub * 4 + qbase + (threadIdx.x & 63)] = 0;
         }
@@ -570,6 +644,9 @@ __device__ __forceinline__ void raster_tile(const RasterArgs &A, const int tile,
         const int bin = (tile_y >> 1) * A.lazy.bin_w + (tile_x >> 1);
         if (A.lazy.bin_more[bin]) redo_tile = bin;
     }
+    if constexpr (LDS_IDS) {
+        if (more.finishes) redo_tile = -1;   // (no launch would read the queue: the bin's own workgroup walks on, below)
+    }
     if (redo_tile >= 0) {
         bool alive = false;
 #pragma unroll
@@ -602,6 +679,14 @@ __device__ __forceinline__ void raster_tile(const RasterArgs &A, const int tile,
         if (A.render_alphas) A.render_alphas[p] = 1.0f - T[qi] * ms::kTUnscale;
         if constexpr (AUX) {
             if (A.last_ids) A.last_ids[p] = last[qi];
+        }
+    }
+    if constexpr (LDS_IDS) {
+        if (more.active) {   // (uniform over the workgroup: all of its waves get here, whatever their own pixels' state)
+            bool ran_dry = false;   // the batch loop ends on `!any_live` unless the ids ran out first
+#pragma unroll
+            for (int qi = 0; qi < NQ; ++qi) ran_dry = ran_dry || __any(kq[qi] != 0.f);
+            more.walk_on(ran_dry, T, kq, pix);
         }
     }
 }
@@ -674,6 +759,25 @@ __global__ __launch_bounds__(64, (CP <= 4 ? (NQ == 2 ? MS_RASTER_MINW2 : AUX ? M
 // The sorted ids still go to flatten_ids (stores nobody waits for): the clean-up launches and the caller's read-back find
 // what they found.  LDS: the eight waves' staging blocks alias the sort's scratch (keys, bucket counters, reduction words);
 // only the ids live through both phases -- 38 144 + 8 192 B a workgroup, three workgroups a CU.
+//
+// A bin whose front is shorter than its list (len < n) FINISHES ITSELF (S.finish_short: a frame without a depth cut whose
+// caller did not ask for the clean-up launch): the verdict "the front ran out with pixels alive" is local to this workgroup,
+// which has the bin's key range, the sort routines and the pixels' state in registers.  After its walk every wave raises a
+// word in LDS if it ran dry on a live pixel; barrier; if the word is up, all 512 threads select and sort the next chunk -- the
+// keys above the last one consumed, the clean-up kernel's own selection (sort_device.hpp, select_next_lds) -- into the scratch
+// the staging blocks alias, its ids go to s_ids, barrier, and every wave that still has a live pixel walks the chunk and
+// stores its pixels again.  Until the word stays down or the list is exhausted.  Every barrier of that loop is reached by all
+// eight waves -- a wave whose block lies outside the image, whose pixels are finished or whose share is empty walks nothing
+// and still takes every barrier -- and what decides the loop is read from LDS behind a barrier, never from a wave's registers.
+// It ends: keys are distinct, every round consumes at least one, and the rounds are capped at n.  A bin sorted whole (almost
+// every bin) pays no barrier and no LDS access for it.  The first continuation counts the bin in redo_count[0] (the next
+// frame's size record reports it and the caller's front level rises as it does behind the clean-up launch) and opens the
+// bin's next-frame cut-off, k_tile_redo's rule; redo_flag / redo_list are not touched (no launch reads them), nor front_count /
+// flatten_ids (the first front's).  The word sits in a staging block's padding beyond the sort's scratch: 46 336 B as before.
+// The chunks are walked WITHOUT the staging blocks, by k_tile_redo's arithmetic (k_rasterize_fwd's generic loop, operation for
+// operation): 64 entries a batch, one per lane, the quad votes, and each quad's set bits read from the staging lane's registers
+// (v_readlane).  Rarely taken, it must cost the walk above it nothing: what it needs of the thread's place is worked out
+// behind an empty asm, in the round that needs it, not ahead of the blend loop and carried through it in registers.
 constexpr int kFusedThreads = 512, kFusedCap = 2048;   // threads (= the sort launch's), ids of LDS room (= its front_cap)
 constexpr size_t kFusedSortLds = (size_t)kFusedCap * 8 + (size_t)kFrontNB * 4 + 64 * 4 + 16;   // (k_tile_front's layout)
 static_assert(SortCfg<kFusedThreads, kFrontK / kFusedThreads>::LDS <= kFusedSortLds, "a short list's whole sort fits the front's scratch");
@@ -694,8 +798,18 @@ __global__ __launch_bounds__(kFusedThreads, 6) void k_sort_rasterize(RasterArgs 
     __builtin_amdgcn_s_setprio(3);
     const int tile = S.order[blockIdx.x];
     int len = 0;   // sorted ids in s_ids (uniform)
+    const int start = A.tile_ranges[2 * tile], n = A.tile_ranges[2 * tile + 1] - start;
+    // (a bin that walks on behind its front) the smallest key not yet consumed, as two scalars
+    bool walks_on = false;
+    uint32_t wlo_lo = 0u, wlo_hi = 0u;
+    // the word a wave raises when its ids ran out on a live pixel: the last staging block's padding (its col[] holds
+    // kSlots * CS floats, rounded up to 16 bytes), which neither staging nor -- beyond kFusedSortLds -- any sort phase writes
+    static_assert(sizeof(Stage::col) >= (Stage::kSlots * Stage::CS + 2) * sizeof(float), "the staging block's padding holds the word");
+    static_assert(sizeof(Stage) * (2 * NW - 1) >= kFusedSortLds, "... beyond the scratch of the sort and of the selection");
+    static_assert((size_t)kRedoCap * 8 + (size_t)kRedoNB * 4 + 4 * NW * 8 + 16 <= kFusedSortLds && kRedoCap <= kFusedCap,
+                  "the next chunk's selection fits the front's scratch, its ids the front's");
+    int *s_more = reinterpret_cast<int *>(&reinterpret_cast<Stage *>(s_scratch)[2 * NW - 1].col[Stage::kSlots * Stage::CS + 1]);
     {
-        const int start = A.tile_ranges[2 * tile], n = A.tile_ranges[2 * tile + 1] - start;
         uint64_t *s_out = reinterpret_cast<uint64_t *>(s_scratch);
         // (k_tile_front's rule for the next frame's cut-off of a bin whose list was sorted whole)
         auto next_cut_whole = [&]() {
@@ -750,6 +864,13 @@ __global__ __launch_bounds__(kFusedThreads, 6) void k_sort_rasterize(RasterArgs 
                     }
                 }
             }
+            if (S.finish_short && len < n) {   // (uniform) this workgroup fetches the rest of its list itself if its pixels ask for it
+                walks_on = true;
+                const unsigned long long wlo = len > 0 ? s_out[len - 1] + 1ull : 0ull;   // (ids are below 2^31: no wrap)
+                wlo_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)wlo);
+                wlo_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(wlo >> 32));
+                if (tid == 0) *s_more = 0;
+            }
         }
         for (int i = tid; i < len; i += kFusedThreads) {
             const int32_t id = (int32_t)(uint32_t)s_out[i];
@@ -768,8 +889,90 @@ __global__ __launch_bounds__(kFusedThreads, 6) void k_sort_rasterize(RasterArgs 
     // workgroup's life into sort and rasterise)
     if (g_diag_stamps && lane == 0) { g_diag_stamps[8 * (size_t)slot + 6] = diag_wg0; g_diag_stamps[8 * (size_t)slot + 7] = diag_wg1; }
 #endif
+    // The rest of a bin that walks on.  Called once by every wave of such a workgroup, behind its walk of the front.
+    auto walk_on = [&](bool ran_dry, auto &T, auto &kq, auto &pix) __attribute__((always_inline)) {
+        int consumed = len;
+        for (int round = 0;; ++round) {
+            // (per round, so that nothing below is worked out ahead of the loop either and kept through the selection)
+            int tid = threadIdx.x, n_keys = n;
+            const uint64_t *kin = S.keys + start;
+            asm volatile("" : "+v"(tid), "+s"(n_keys), "+s"(kin));
+            const int lane = tid & 63, lx = lane & 7, ly = lane >> 3, sub = tid >> 7, qbase = ((tid >> 6) & 1) * 2;
+            const int tile_y = tile / A.tw, tile_x = tile - tile_y * A.tw;
+            // (a fused frame is on 32-px bins, 2 x 2 blocks a bin, two waves a block: rasterize_fwd requires it of every frame it
+            // hands this kernel -- raster_tile's mapping w >> 1, w & 1 of the call below, restated from the hidden thread index)
+            static_assert(kFusedThreads == 8 * 64, "eight waves: four blocks of two waves");
+            const int bx = tile_x * 32 + (sub & 1) * 16, by = tile_y * 32 + (sub >> 1) * 16;
+            const float fbx = (float)bx + 0.5f, fby = (float)by + 0.5f;
+            uint64_t *s_key = reinterpret_cast<uint64_t *>(s_scratch);
+            uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_key + kRedoCap);
+            unsigned long long *s_red = reinterpret_cast<unsigned long long *>(s_cnt + kRedoNB);
+            int *s_sel = reinterpret_cast<int *>(s_red + 4 * NW);
+            auto each_key = [&](auto &&fn) __attribute__((always_inline)) {
+                for (int i = tid; i < n_keys; i += kFusedThreads) fn(kin[i]);
+            };
+            if (ran_dry && lane == 0) *s_more = 1;
+            __syncthreads();   // every wave has walked its ids and stored its pixels: the word is final, the staging blocks are free
+            const int asked = *s_more;   // (uniform: LDS behind a barrier; cleared only behind the selection's barriers)
+            if (!asked || consumed >= n_keys || round >= n_keys) break;
+            if (tid == 0 && round == 0) {
+                atomicAdd(A.lazy.redo_count, 1);                    // reported with the next frame's size record, word 5
+                if (S.tau_out) S.tau_out[tile] = 0xffffffffu;       // the next frame keeps every pair of this bin
+            }
+            const int F = select_next_lds<kFusedThreads>(each_key, tid, ((unsigned long long)wlo_hi << 32) | wlo_lo, s_key, s_cnt, s_red, s_sel);
+            if (F == 0) break;   // (uniform) no key is left
+            const unsigned long long next_lo = s_key[F - 1] + 1ull;
+            for (int i = tid; i < F; i += kFusedThreads) s_ids[i] = (int32_t)(uint32_t)s_key[i];
+            if (tid == 0) *s_more = 0;
+            wlo_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)next_lo);
+            wlo_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(next_lo >> 32));
+            consumed += F;
+            __syncthreads();   // the ids are in place and the word is down; from here to the loop's top the waves are on their own
+            for (int b0 = 0; b0 < F; b0 += kBatch) {
+                if (!(__any(kq[0] != 0.f) || __any(kq[1] != 0.f))) break;
+                float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = ra, rc = ra;
+                int hit = 0;
+                if (b0 + lane < F) {
+                    const int g = min(max(s_ids[b0 + lane], 0), A.n_gauss - 1);
+                    const float4 *rec = A.records + 3 * (size_t)g;
+                    ra = rec[0]; rb = rec[1]; rc = rec[2];
+                    hit = record_reach<2>(ra, rb, rc, fbx, fby, qbase);   // (the wave's two quads)
+                }
+#pragma unroll
+                for (int qi = 0; qi < 2; ++qi) {
+                    if (!__any(kq[qi] != 0.f)) continue;
+                    const int q = qbase + qi;
+                    const float px = (float)(bx + lx + (q & 1) * 8) + 0.5f, py = (float)(by + ly + (q >> 1) * 8) + 0.5f;
+                    unsigned long long hm = __ballot((hit >> qi) & 1);
+                    while (hm) {
+                        const int j = __builtin_ctzll(hm);
+                        hm &= hm - 1ull;
+                        auto from = [&](float v) __attribute__((always_inline)) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j)); };
+                        const float vis = blend_entry(from(ra.x), from(ra.y), from(ra.z), from(ra.w), from(rb.x), from(rb.y), px, py, T[qi], kq[qi]);
+                        pix[qi][0] += from(rb.z) * vis;
+                        pix[qi][1] += from(rb.w) * vis;
+                        pix[qi][2] += from(rc.x) * vis;
+                    }
+                }
+            }
+            ran_dry = __any(kq[0] != 0.f) || __any(kq[1] != 0.f);
+#pragma unroll
+            for (int qi = 0; qi < 2; ++qi) {
+                const int q = qbase + qi;
+                const int X = bx + lx + (q & 1) * 8, Y = by + ly + (q >> 1) * 8;
+                if (X >= A.W || Y >= A.H) continue;
+                const size_t p = (size_t)Y * A.W + X;
+#pragma unroll
+                for (int k = 0; k < CP; ++k)
+                    if (k < A.cdim)
+                        A.render_colors[p * A.cdim + k] = finish_channel(pix[qi][k], T[qi], A.backgrounds ? A.backgrounds[k] : 0.f);
+                if (A.render_alphas) A.render_alphas[p] = 1.0f - T[qi] * ms::kTUnscale;
+            }
+        }
+    };
     raster_tile<CP, ColorT, false, 2, PACKED, false, true>(A, tile, w >> 1, w & 1, reinterpret_cast<Stage *>(s_scratch) + 2 * w, slot,
-                                                            r_a, r_b, r_c, r_g, s_ids, len);
+                                                            r_a, r_b, r_c, r_g, s_ids, len,
+                                                            RasterMore<decltype(walk_on)>{S.finish_short != 0, walks_on, walk_on});
 }
 
 // ---- clean-up pass of a lazily sorted frame -----------------------------------------------------
@@ -788,7 +991,7 @@ __global__ __launch_bounds__(kFusedThreads, 6) void k_sort_rasterize(RasterArgs 
 // written in the order of 2 048 key buckets into the tile's slots of the id array (nobody reads the ids of a redone
 // tile any more: the rasteriser is done, the clean-up stages from the keys), the buckets' starts stay in LDS, and
 // every chunk is then selected from the buckets that hold the next ~1 024 keys alone.
-constexpr int kRedoChunk = 1024, kRedoCap = 2048, kRedoNB = 2048, kRedoPartMin = 4096;
+constexpr int kRedoPartMin = 4096;   // (kRedoChunk, kRedoCap, kRedoNB: sort_device.hpp, with the selection)
 
 // Round 4: TWO launches where the lists are long.  One workgroup per bin walking the bin's 16x16 blocks one after the
 // other, every chunk selected and ranked afresh for each block, made the frame after a scene swap the heaviest bin's
@@ -1108,31 +1311,8 @@ __global__ __launch_bounds__(256) void k_tile_redo(RasterArgs A) {
                         // which of the block's four 8x8 quads the entry can reach at all: the forward kernel's
                         // exact ellipse-vs-quad test on the record's three numbers (log2 units) -- a wave skips
                         // what cannot blend in its quad (a 64-px bin's list is ~94 % misses for any one quad)
-                        int hit = 0;
-                        const float smax = rc.y, nb_c = rc.z, nb_a = rc.w;
-                        if (smax == kInf) {
-                            hit = 0xf;
-                        } else if (smax > -kInf) {
-                            const float fbx = (float)(tile_x * A.ts + sub_x * 16) + 0.5f, fby = (float)(tile_y * A.ts + sub_y * 16) + 0.5f;
-#pragma unroll
-                            for (int qq = 0; qq < 4; ++qq) {
-                                const float xl = fbx + (float)((qq & 1) * 8) - ra.x, xh = xl + 7.0f;
-                                const float yl = fby + (float)((qq >> 1) * 8) - ra.y, yh = yl + 7.0f;
-                                const bool in_x = xl <= 0.f && xh >= 0.f, in_y = yl <= 0.f && yh >= 0.f;
-                                float best = (in_x && in_y) ? 0.f : 3.0e38f;
-                                if (!in_x) {
-                                    const float ddx = xl > 0.f ? xl : xh;
-                                    const float ddy = fminf(fmaxf(nb_c * ddx, yl), yh);
-                                    best = -(ra.z * ddx * ddx + rb.x * ddy * ddy + ra.w * ddx * ddy);
-                                }
-                                if (!in_y) {
-                                    const float ddy = yl > 0.f ? yl : yh;
-                                    const float ddx = fminf(fmaxf(nb_a * ddy, xl), xh);
-                                    best = fminf(best, -(ra.z * ddx * ddx + rb.x * ddy * ddy + ra.w * ddx * ddy));
-                                }
-                                hit |= (best <= smax) ? (1 << qq) : 0;
-                            }
-                        }
+                        const float fbx = (float)(tile_x * A.ts + sub_x * 16) + 0.5f, fby = (float)(tile_y * A.ts + sub_y * 16) + 0.5f;
+                        const int hit = record_reach<4>(ra, rb, rc, fbx, fby, 0);
                         s_pa[tid] = ra;
                         s_pb[tid] = make_float4(rb.x, rc.y > -kInf && listed ? rb.y : -kInf, __int_as_float(hit), 0.f);
                         s_pc[tid * CP] = rb.z; s_pc[tid * CP + 1] = rb.w; s_pc[tid * CP + 2] = rc.x;
@@ -1172,20 +1352,9 @@ __global__ __launch_bounds__(256) void k_tile_redo(RasterArgs A) {
                     hm &= hm - 1ull;
                     const float4 rb = s_pb[t];
                     const float4 ra = s_pa[t];
-                    const float dx = ra.x - px, dy = ra.y - py;
-                    const float la = fmaf(dx, fmaf(ra.z, dx, ra.w * dy), fmaf(rb.x * dy, dy, rb.y));
-                    // k_rasterize_fwd's generic (CHECK) arithmetic, operation for operation
-                    float alpha = fminf(ms::kMaxAlpha, __builtin_amdgcn_exp2f(la));
-                    alpha = la <= rb.y ? alpha : 0.f;
-                    const float mj = alpha * kq;
-                    const float vj = mj * T;
-                    const float nt = fmaf(vj, -ms::kAlphaOfV, T);
-                    const bool dead = !(nt > ms::kTransmittanceStop * ms::kTScale);
-                    const float vis = dead ? 0.f : vj;
-                    kq = dead ? 0.f : kq;
+                    const float vis = blend_entry(ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, px, py, T, kq);
 #pragma unroll
                     for (int k = 0; k < CP; ++k) pix[k] += s_pc[t * CP + k] * vis;
-                    T = dead ? T : nt;
                   }
                 }
             };
@@ -1220,7 +1389,7 @@ __global__ __launch_bounds__(256) void k_tile_redo(RasterArgs A) {
             for (; !sorted;) {
                 // ---- (1) next chunk: window [wlo, whi] over eligible keys
                 if (!first && lower == ~0ull) break;   // nothing can follow the largest key (and lower + 1 would wrap)
-                unsigned long long wlo = first ? 0ull : lower + 1ull, whi = ~0ull;
+                const unsigned long long wlo = first ? 0ull : lower + 1ull;
                 if (part) {
                     // the buckets the next chunk can come from: the one the last consumed key lies in (its remaining
                     // keys pass the `wlo` filter) and as many after it as hold kRedoChunk keys (or all that are left)
@@ -1234,112 +1403,9 @@ __global__ __launch_bounds__(256) void k_tile_redo(RasterArgs A) {
                     w0 = (int)s_bstart[cb];
                     w1 = (int)s_bstart[lo_b + 1];
                 }
-                int bstar = -1, F = 0;
-                unsigned long long kmin = 0ull;
-                int shift = 0;
-                bool none = false;
-                for (;;) {
-                    unsigned long long mn = ~0ull, mx = 0ull;
-                    unsigned int cnt = 0;
-                    each_key([&](unsigned long long k) {
-                        if (k >= wlo && k <= whi) { mn = k < mn ? k : mn; mx = k > mx ? k : mx; ++cnt; }
-                    });
-#pragma unroll
-                    for (int d = 32; d > 0; d >>= 1) {
-                        const unsigned long long omn = __shfl_xor(mn, d), omx = __shfl_xor(mx, d);
-                        mn = omn < mn ? omn : mn;
-                        mx = omx > mx ? omx : mx;
-                        cnt += (unsigned int)__shfl_xor((int)cnt, d);
-                    }
-                    __syncthreads();   // previous users of s_red / s_cnt / s_sel are done
-                    if (lane == 0) { s_red[w] = mn; s_red[4 + w] = mx; s_red[8 + w] = cnt; }
-                    for (int b = tid; b < kRedoNB; b += 256) s_cnt[b] = 0;
-                    if (tid == 0) { s_sel[0] = -1; s_sel[1] = 0; s_sel[2] = -1; s_sel[3] = 0; }
-                    __syncthreads();
-                    unsigned long long total = 0;
-                    mn = ~0ull; mx = 0ull;
-#pragma unroll
-                    for (int ww = 0; ww < 4; ++ww) {
-                        mn = s_red[ww] < mn ? s_red[ww] : mn;
-                        mx = s_red[4 + ww] > mx ? s_red[4 + ww] : mx;
-                        total += s_red[8 + ww];
-                    }
-                    if (total == 0) { none = true; break; }   // uniform
-                    kmin = mn;
-                    const unsigned long long span = mx - mn;
-                    const int bits = span ? 64 - __clzll((long long)span) : 0;
-                    shift = max(0, bits - 11);
-                    each_key([&](unsigned long long k) {
-                        if (k >= wlo && k <= whi) atomicAdd(&s_cnt[(unsigned int)((k - kmin) >> shift)], 1u);
-                    });
-                    __syncthreads();
-                    // exclusive scan of 2048 counters: thread t owns buckets 8t .. 8t+7
-                    unsigned int c[8], sum = 0;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) { c[j] = s_cnt[8 * tid + j]; sum += c[j]; }
-                    unsigned int incl = sum;
-#pragma unroll
-                    for (int d = 1; d < 64; d <<= 1) {
-                        const unsigned int o = (unsigned int)__shfl_up((int)incl, d);
-                        if (lane >= d) incl += o;
-                    }
-                    __syncthreads();
-                    if (lane == 63) s_red[12 + w] = incl;
-                    __syncthreads();
-                    unsigned int run = incl - sum;
-#pragma unroll
-                    for (int ww = 0; ww < 4; ++ww)
-                        if (ww < w) run += (unsigned int)s_red[12 + ww];
-                    const unsigned int want = total < (unsigned long long)kRedoChunk ? (unsigned int)total : (unsigned int)kRedoChunk;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const unsigned int e = run, i2 = run + c[j];
-                        if (c[j] && e == 0) { s_sel[2] = 8 * tid + j; s_sel[3] = (int)c[j]; }   // first non-empty bucket
-                        if (c[j] && e < want && i2 >= want) {
-                            if (i2 <= (unsigned int)kRedoCap) { s_sel[0] = 8 * tid + j; s_sel[1] = (int)i2; }
-                            else { s_sel[0] = 8 * tid + j - 1; s_sel[1] = (int)e; }
-                        }
-                        s_cnt[8 * tid + j] = e;
-                        run = i2;
-                    }
-                    __syncthreads();
-                    bstar = s_sel[0]; F = s_sel[1];
-                    if (F > 0) break;
-                    // the first bucket alone overflows the chunk: narrow the window into it and retry
-                    const unsigned long long blo = kmin + ((unsigned long long)s_sel[2] << shift);
-                    wlo = blo > wlo ? blo : wlo;
-                    const unsigned long long bhi = shift ? blo + ((1ull << shift) - 1ull) : blo;
-                    whi = bhi < whi ? bhi : whi;
-                }
-                if (none) break;
-                // gather + rank
-                each_key([&](unsigned long long k) {
-                    if (k >= wlo && k <= whi) {
-                        const int b = (int)((k - kmin) >> shift);
-                        if (b <= bstar) s_key[atomicAdd(&s_cnt[b], 1u)] = k;
-                    }
-                });
-                __syncthreads();
-                unsigned long long kk[kRedoCap / 256];
-                int dest[kRedoCap / 256];
-#pragma unroll
-                for (int e = 0; e < kRedoCap / 256; ++e) {
-                    const int i = e * 256 + tid;
-                    dest[e] = -1;
-                    if (i < F) {
-                        kk[e] = s_key[i];
-                        const int b = (int)((kk[e] - kmin) >> shift);
-                        const int beg = b ? (int)s_cnt[b - 1] : 0, en = (int)s_cnt[b];
-                        int r = 0;
-                        for (int j = beg; j < en; ++j) r += s_key[j] < kk[e] ? 1 : 0;
-                        dest[e] = beg + r;
-                    }
-                }
-                __syncthreads();
-#pragma unroll
-                for (int e = 0; e < kRedoCap / 256; ++e)
-                    if (dest[e] >= 0) s_key[dest[e]] = kk[e];
-                __syncthreads();
+                // (sort_device.hpp: the selection this kernel shares with the fused kernel's bins that walk on behind their fronts)
+                const int F = select_next_lds<256>(each_key, tid, wlo, s_key, s_cnt, s_red, s_sel);
+                if (F == 0) break;   // (uniform) no key is left
                 lower = s_key[F - 1];
                 first = false;
                 // ---- (2) composite the chunk, 256 entries staged at a time
@@ -1456,7 +1522,9 @@ void launch_cp(const RasterArgs &A_in, hipStream_t stream, void *after_raster_ev
         // lazily sorted frame: redo the (normally zero) tiles whose front did not saturate them
         // (measured by leaving it out: the launch costs the frame 2.4 us -- 0.1826 -> 0.1802 ms at config 3 -- although
         // rocprofv3 shows the empty kernel at 4.5 us)
-        if (A.lazy.front_count) {
+        // (a fused frame whose bins finish their own short fronts has nothing to redo: no launch, none stashed)
+        const bool in_kernel = CP == 3 && fused && fused->finish_short;
+        if (A.lazy.front_count && !in_kernel) {
             if (A.lazy.verdict) stash_cleanup(A, &cleanup_launches<CP, ColorT>);   // (deferred: rasterize_deferred_cleanup)
             else cleanup_launches<CP, ColorT>(A, stream);
         }
@@ -1585,7 +1653,7 @@ int ms::rasterize_fwd(int64_t N, int64_t M, int64_t density_hint, const float *m
     if (fused) {
         // the frame's sort was left to this launch: the caller asked rasterize_takes_sort first, and the rest is what it could not see
         MS_REQUIRE(A.records && lazy && lazy->front_count && lazy->front_threshold == kFrontK && order && !last_ids && !A.quad_lists &&
-                       !zero_mem && tile_size == 32 && fused->n_order == band_tiles && fused->fp.front_cap <= kFusedCap && M == fused->cap,
+                       !zero_mem && clip_row16_begin < 0 && tile_size == 32 && fused->n_order == band_tiles && fused->fp.front_cap <= kFusedCap && M == fused->cap,
                    MS_ERR_INVALID_ARG, "rasterize_fwd: this frame cannot sort its bins in the rasteriser");
         A.parts = 2;
     }

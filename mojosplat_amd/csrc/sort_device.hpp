@@ -410,4 +410,133 @@ __device__ __forceinline__ int front_select_lds(const uint64_t *__restrict__ kin
     return F;
 }
 
+// ---- the next chunk of a list that is consumed in depth order without ever being sorted whole ---------------------
+// (rasterize.hip: the clean-up kernel k_tile_redo at 256 threads, and a bin of the fused kernel k_sort_rasterize that walks on
+// behind its sorted front at 512)
+// The ~kRedoChunk smallest of the list's keys >= wlo, sorted, in s_key[0, F): range of the eligible 64-bit keys, LDS histogram
+// over kRedoNB order-preserving buckets, prefix, the buckets up to the one that completes the chunk (at most kRedoCap keys) --
+// or, if the FIRST bucket alone overflows the room, the same again inside that bucket (keys are distinct, so a bucket that
+// spans one key value holds one key: the narrowing terminates; the id half of the key decides among bit-equal depths) -- and
+// every selected key ranked inside its bucket.  -> F, or 0: no key >= wlo is left.  Any list length, any depth distribution.
+// each_key(fn): calls fn(key) for this thread's share of the list (or of a slice of it that holds the next chunk), the same
+// share on every call.  Every thread of the THREADS-thread workgroup; s_key: kRedoCap keys, s_cnt: kRedoNB words, s_red:
+// 4 * THREADS / 64 words of 64 bits, s_sel: 4 words of LDS.  The first barrier comes before the first write to any of them.
+// tid: threadIdx.x (the caller's copy: the fused kernel hands over one the compiler cannot see through, so that nothing of
+// this rarely taken code is computed ahead of its hot loop and kept in registers across it).
+constexpr int kRedoChunk = 1024, kRedoCap = 2048, kRedoNB = 2048;
+
+template <int THREADS, typename EachKey>
+__device__ __forceinline__ int select_next_lds(EachKey &&each_key, const int tid, unsigned long long wlo, uint64_t *s_key,
+                                               uint32_t *s_cnt, unsigned long long *s_red, int *s_sel) {
+    constexpr int NW = THREADS / 64, kBpt = kRedoNB / THREADS, kRank = kRedoCap / THREADS;
+    static_assert(kBpt * THREADS == kRedoNB && kRank * THREADS == kRedoCap && NW >= 1, "buckets and keys divide over the threads");
+    const int lane = tid & 63, w = tid >> 6;
+    unsigned long long whi = ~0ull;
+    int bstar = -1, F = 0;
+    unsigned long long kmin = 0ull;
+    int shift = 0;
+    for (;;) {
+        unsigned long long mn = ~0ull, mx = 0ull;
+        unsigned int cnt = 0;
+        each_key([&](unsigned long long k) {
+            if (k >= wlo && k <= whi) { mn = k < mn ? k : mn; mx = k > mx ? k : mx; ++cnt; }
+        });
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+            const unsigned long long omn = __shfl_xor(mn, d), omx = __shfl_xor(mx, d);
+            mn = omn < mn ? omn : mn;
+            mx = omx > mx ? omx : mx;
+            cnt += (unsigned int)__shfl_xor((int)cnt, d);
+        }
+        __syncthreads();   // previous users of s_red / s_cnt / s_sel are done
+        if (lane == 0) { s_red[w] = mn; s_red[NW + w] = mx; s_red[2 * NW + w] = cnt; }
+        for (int b = tid; b < kRedoNB; b += THREADS) s_cnt[b] = 0;
+        if (tid == 0) { s_sel[0] = -1; s_sel[1] = 0; s_sel[2] = -1; s_sel[3] = 0; }
+        __syncthreads();
+        unsigned long long total = 0;
+        mn = ~0ull; mx = 0ull;
+#pragma unroll
+        for (int ww = 0; ww < NW; ++ww) {
+            mn = s_red[ww] < mn ? s_red[ww] : mn;
+            mx = s_red[NW + ww] > mx ? s_red[NW + ww] : mx;
+            total += s_red[2 * NW + ww];
+        }
+        if (total == 0) return 0;   // uniform
+        kmin = mn;
+        const unsigned long long span = mx - mn;
+        const int bits = span ? 64 - __clzll((long long)span) : 0;
+        shift = max(0, bits - 11);
+        each_key([&](unsigned long long k) {
+            if (k >= wlo && k <= whi) atomicAdd(&s_cnt[(unsigned int)((k - kmin) >> shift)], 1u);
+        });
+        __syncthreads();
+        // exclusive scan of the counters: thread t owns buckets kBpt t .. kBpt t + kBpt - 1
+        unsigned int c[kBpt], sum = 0;
+#pragma unroll
+        for (int j = 0; j < kBpt; ++j) { c[j] = s_cnt[kBpt * tid + j]; sum += c[j]; }
+        unsigned int incl = sum;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned int o = (unsigned int)__shfl_up((int)incl, d);
+            if (lane >= d) incl += o;
+        }
+        __syncthreads();
+        if (lane == 63) s_red[3 * NW + w] = incl;
+        __syncthreads();
+        unsigned int run = incl - sum;
+#pragma unroll
+        for (int ww = 0; ww < NW; ++ww)
+            if (ww < w) run += (unsigned int)s_red[3 * NW + ww];
+        const unsigned int want = total < (unsigned long long)kRedoChunk ? (unsigned int)total : (unsigned int)kRedoChunk;
+#pragma unroll
+        for (int j = 0; j < kBpt; ++j) {
+            const unsigned int e = run, i2 = run + c[j];
+            if (c[j] && e == 0) { s_sel[2] = kBpt * tid + j; s_sel[3] = (int)c[j]; }   // first non-empty bucket
+            if (c[j] && e < want && i2 >= want) {
+                if (i2 <= (unsigned int)kRedoCap) { s_sel[0] = kBpt * tid + j; s_sel[1] = (int)i2; }
+                else { s_sel[0] = kBpt * tid + j - 1; s_sel[1] = (int)e; }
+            }
+            s_cnt[kBpt * tid + j] = e;
+            run = i2;
+        }
+        __syncthreads();
+        bstar = s_sel[0]; F = s_sel[1];
+        if (F > 0) break;
+        // the first bucket alone overflows the chunk: narrow the window into it and retry
+        const unsigned long long blo = kmin + ((unsigned long long)s_sel[2] << shift);
+        wlo = blo > wlo ? blo : wlo;
+        const unsigned long long bhi = shift ? blo + ((1ull << shift) - 1ull) : blo;
+        whi = bhi < whi ? bhi : whi;
+    }
+    // gather + rank
+    each_key([&](unsigned long long k) {
+        if (k >= wlo && k <= whi) {
+            const int b = (int)((k - kmin) >> shift);
+            if (b <= bstar) s_key[atomicAdd(&s_cnt[b], 1u)] = k;
+        }
+    });
+    __syncthreads();
+    unsigned long long kk[kRank];
+    int dest[kRank];
+#pragma unroll
+    for (int e = 0; e < kRank; ++e) {
+        const int i = e * THREADS + tid;
+        dest[e] = -1;
+        if (i < F) {
+            kk[e] = s_key[i];
+            const int b = (int)((kk[e] - kmin) >> shift);
+            const int beg = b ? (int)s_cnt[b - 1] : 0, en = (int)s_cnt[b];
+            int r = 0;
+            for (int j = beg; j < en; ++j) r += s_key[j] < kk[e] ? 1 : 0;
+            dest[e] = beg + r;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < kRank; ++e)
+        if (dest[e] >= 0) s_key[dest[e]] = kk[e];
+    __syncthreads();
+    return F;
+}
+
 }  // namespace
