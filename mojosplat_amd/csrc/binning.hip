@@ -76,12 +76,8 @@ static_assert(kClaimGroups == 8 || kClaimGroups == 4 || kClaimGroups == 2 || kCl
 constexpr int kMaxG = 512;
 constexpr int kSmallCapDecl = 1024, kMediumCapDecl = 8192, kLargeCapDecl = 16384;  // per-tile sort classes
 constexpr int kCoopThreshold = 32; // boxes touching more tiles are walked by a whole wave
-constexpr int kBandCull = 32;      // bit of the `tight` flags: the band's Gaussians were pre-culled (k_band_precull)
 constexpr int kLightBucket = 32;   // length bucket (4 per octave) of the longest LIGHT list: 255 entries
 constexpr int kLightCap = 256;     // ... sorted by ONE wave (sort_segment_lds<64, 4>), eight lists to a workgroup
-constexpr int kLean = 64;          // ... the frame keeps LeanRecs instead of the projected arrays (internal: ms_render_fwd)
-constexpr int kDeferTotal = 128;   // ... the scans' total pass rides in the scatter launch (internal: sync-free frames)
-static_assert(kLean == ms::kTightLean && kDeferTotal == ms::kTightDeferTotal, "internal flag bits out of sync");
 constexpr size_t kMaxLds = 160 * 1024 - 4096;   // dynamic LDS of the binning kernels: the CU's 160 KB less their static blocks (segment prefix of a band's candidate list, wave totals)
 
 struct Grid {
@@ -2044,20 +2040,14 @@ __global__ __launch_bounds__(256) void k_offset_encode(int64_t M, const int64_t 
 }
 
 // ---- host side ----------------------------------------------------------------------
-struct Plan {
-    int G;
-    int64_t chunk;
-    int64_t near_cap;   // depth-cut frames: the stride of a count workgroup's compacted records (>= what any workgroup walks, band candidates included)
-    int T, T_local;
-    size_t lds_bytes;
-    size_t off_xtot;   // claimed rows: eight arrays of T counters, one per XCD
-    size_t off_hist, off_count, off_medium, off_large, off_xl, off_on_grid, off_mask, off_front, off_redo_flag,
-        off_redo_list, off_redo_count, off_depth_wg, off_order, off_tau, off_has_far, off_wg_far, off_far_seg, off_cand_count, off_cand, off_lean, off_near, total;
-};
+using ms::Band;
+using ms::Schedule;
 
-bool make_plan(int64_t N, int tw, int th, int row_begin, int row_end, Plan &p) {
-    p.T = tw * th;
-    p.T_local = (row_end - row_begin) * tw;
+// How the count and scatter kernels walk the scene for a band: it depends on the band's rows, the workspace's layout does not
+Schedule make_schedule(const Band &b) {
+    const int64_t N = b.N;
+    Schedule p;
+    p.T_local = (b.row_end - b.row_begin) * b.tw;
     p.lds_bytes = (size_t)p.T_local * 4 + 16;  // + the on-grid counter of the count kernels
     int64_t G = ms::ceil_div(N > 0 ? N : 1, MS_CHUNK);
     // scenes too small to give every CU a workgroup at MS_CHUNK Gaussians each (100k: 49 workgroups on 256 CUs,
@@ -2068,42 +2058,74 @@ bool make_plan(int64_t N, int tw, int th, int row_begin, int row_end, Plan &p) {
     p.chunk = ms::ceil_div(N > 0 ? N : 1, G);
     p.G = (int)ms::ceil_div(N > 0 ? N : 1, p.chunk);
     p.near_cap = ms::ceil_div(ms::ceil_div(N > 0 ? N : 1, (int64_t)kHistThreads), (int64_t)p.G) * kHistThreads;
-    // workspace carve-up is sized for the FULL grid so one buffer serves any band
-    size_t o = 0;
-    p.off_hist = o;   o += ms::align_up((size_t)kMaxG * p.T * 4, 256);
-    p.off_count = o;  o += ms::align_up((size_t)p.T * 4, 256);
-    p.off_xtot = o;   o += ms::align_up((size_t)8 * p.T * 4, 256);
-    p.off_medium = o; o += ms::align_up((size_t)p.T * 4, 256);
-    p.off_large = o;  o += ms::align_up((size_t)p.T * 4, 256);
-    p.off_xl = o;     o += ms::align_up((size_t)p.T * 4, 256);
-    p.off_on_grid = o; o += ms::align_up((size_t)kMaxG * 4 + 64, 256);   // + the scan kernel's arrival ticket (word kMaxG)
-    p.off_front = o;      o += ms::align_up((size_t)p.T * 4, 256);  // lazy sorting: sorted-front length per tile
-    p.off_redo_flag = o;  o += ms::align_up((size_t)p.T * 4, 256);  //   tiles whose front did not saturate them
-    p.off_redo_list = o;  o += ms::align_up((size_t)p.T * 4, 256);
-    p.off_redo_count = o; o += 256;
-    p.off_depth_wg = o;   o += ms::align_up((size_t)kMaxG * 8, 256);   // per-workgroup depth-bit min / max (k_isect_scatter)
-    p.off_order = o;      o += ms::align_up((size_t)p.T * 4, 256);     // the band's tiles, heaviest first (rasteriser launch order)
-    p.off_tau = o;        o += ms::align_up((size_t)p.T * 8, 256);     // depth cut: per tile, the depth bits behind which a pair is "far" -- two buffers of T words:
-                                                                       //   a frame reads the one the previous frame's sort kernel wrote and writes the other
-    p.off_has_far = o;    o += ms::align_up((size_t)p.T * 4, 256);     //   this frame's tiles that own far pairs
-    p.off_wg_far = o;     o += ms::align_up((size_t)kMaxG * 8, 256);   //   far pairs per count workgroup | records that keep a pair per count workgroup
-    p.off_far_seg = o;    o += ms::align_up((size_t)p.T * 12, 256);    //   clean-up: regenerated far pairs per tile -- count, cursor (zeroed by the frame's total pass), start
-    // (the only N-dependent block comes last: everything above -- the clean-up count among it, which a caller
-    // reads back one frame later -- stays where it is when the scene grows or shrinks on a fixed grid)
-    p.off_cand_count = o; o += ms::align_up((size_t)kMaxG * 4, 256);   // band pre-cull: survivors per segment
-    p.off_mask = o;   o += ms::align_up((size_t)(N > 0 ? N : 1) * 8, 256);  // tight binning: reach masks
-    p.off_cand = o;   o += ms::align_up((size_t)(N > 0 ? N : 1) * 4, 256);  // band pre-cull: candidate list
-    p.off_lean = o;   o += ms::align_up((size_t)(N > 0 ? N : 1) * sizeof(LeanRec), 256);  // lean frames: box + depth per position
-    p.off_near = o;   o += ms::align_up((size_t)((N > 0 ? N : 1) + (int64_t)kHistThreads * (kMaxG + 1)) * sizeof(LeanRec), 256);  // depth-cut frames: the records that keep a pair, compacted per count workgroup (G strides of near_cap)
-    p.total = o;
-    return p.lds_bytes <= kMaxLds;
+    return p;
+}
+bool fits_lds(const Schedule &s) { return s.lds_bytes <= kMaxLds; }
+
+// The isect workspace of a scene of N Gaussians on a tw x th grid as a typed view: every array by name, carved up here and
+// nowhere else.  Sized for the FULL grid so one buffer serves any band; `total` is ms_isect_workspace_bytes (ABI): order,
+// sizes and the 256-byte alignment are fixed.  (A null workspace gives the size alone; its pointers are never followed.)
+struct Layout {
+    size_t T, total;
+    uint32_t *hist, *count, *claims, *on_grid, *depth_wg, *tau, *has_far, *wg_far, *far_seg;
+    int32_t *medium, *large, *xl, *front_count, *redo_flag, *redo_list, *redo_count, *order, *cand_count, *cand_ids;
+    unsigned long long *masks;
+    LeanRec *lean_recs, *near_recs;
+    explicit Layout(const Band &b) : T((size_t)(b.tw * b.th)), total(0) {
+        const size_t n = (size_t)(b.N > 0 ? b.N : 1);
+        auto take = [&](auto *&p, size_t bytes) {
+            p = reinterpret_cast<std::remove_reference_t<decltype(p)>>((uintptr_t)b.ws + total);
+            total += ms::align_up(bytes, 256);
+        };
+        take(hist, (size_t)kMaxG * T * 4);
+        take(count, T * 4);
+        take(claims, 8 * T * 4);                // claimed rows: eight arrays of T counters, one per XCD
+        take(medium, T * 4);
+        take(large, T * 4);
+        take(xl, T * 4);
+        take(on_grid, (size_t)kMaxG * 4 + 64);  // per count workgroup + scan_ticket() and light_count()
+        take(front_count, T * 4);               // lazy sorting: sorted-front length per tile
+        take(redo_flag, T * 4);                 //   tiles whose front did not saturate them
+        take(redo_list, T * 4);
+        take(redo_count, 256);                  //   words 0-2: the clean-up's counts; from byte 64: claim_flag()
+        take(depth_wg, (size_t)kMaxG * 8);      // per-workgroup depth-bit min / max (k_isect_scatter)
+        take(order, T * 4);                     // the band's tiles, heaviest first (rasteriser launch order)
+        take(tau, T * 8);                       // depth cut: cutoffs(0) and cutoffs(1)
+        take(has_far, T * 4);                   //   this frame's tiles that own far pairs
+        take(wg_far, (size_t)kMaxG * 8);        //   far pairs per count workgroup | records that keep a pair per count workgroup
+        take(far_seg, T * 12);                  //   clean-up: regenerated far pairs per tile -- count, cursor (zeroed by the frame's total pass), start
+        // (the only N-dependent blocks come last: everything above -- the clean-up count among it, which a caller
+        // reads back one frame later -- stays where it is when the scene grows or shrinks on a fixed grid)
+        take(cand_count, (size_t)kMaxG * 4);    // band pre-cull: survivors per segment
+        take(masks, n * 8);                     // tight binning: reach masks
+        take(cand_ids, n * 4);                  // band pre-cull: candidate list
+        take(lean_recs, n * sizeof(LeanRec));   // lean frames: box + depth per position
+        // depth-cut frames: the records that keep a pair, compacted per count workgroup (G strides of near_cap)
+        take(near_recs, (n + (size_t)kHistThreads * (kMaxG + 1)) * sizeof(LeanRec));
+    }
+    uint32_t *scan_ticket() const { return on_grid + kMaxG; }       // k_tile_scan_wg's arrival counter
+    uint32_t *light_count() const { return on_grid + kMaxG + 1; }   // the light lists the total pass counted
+    unsigned long long *claim_flag() const { return reinterpret_cast<unsigned long long *>(redo_count + 16); }   // (two words, 8-byte aligned)
+    // depth cut: per tile, the depth bits behind which a pair is "far" -- two buffers of T words: a frame reads the one the
+    // previous frame's sort kernel wrote and writes the other
+    uint32_t *cutoffs(int buf) const { return tau + (size_t)buf * T; }
+    // the band's candidate list as the count launch with schedule `s` left it
+    Candidates candidates(const Schedule &s) const { return Candidates{cand_ids, cand_count, s.G, s.chunk}; }
+};
+
+// what a band needs to run: its counters in the count / scatter kernels' LDS, the whole layout in its workspace
+int check_band(const Band &b, const Schedule &s, const Layout &L, const char *who) {
+    MS_REQUIRE(fits_lds(s), MS_ERR_TOO_LARGE, "%s: band of %d tiles needs %zu B of LDS (max %zu); bin in row bands", who, s.T_local,
+               s.lds_bytes, kMaxLds);
+    MS_REQUIRE(b.ws_bytes >= L.total, MS_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, b.ws_bytes, L.total);
+    return MS_OK;
 }
 
-int check_grid(int tile_size, int tw, int th, int row_begin, int row_end) {
-    MS_REQUIRE(tile_size > 0 && tw > 0 && th > 0, MS_ERR_INVALID_ARG, "isect: bad tile grid");
-    MS_REQUIRE((int64_t)tw * th < (1ll << 30), MS_ERR_TOO_LARGE, "isect: tile grid too large");
-    MS_REQUIRE(row_begin >= 0 && row_begin <= row_end && row_end <= th, MS_ERR_INVALID_ARG,
-               "isect: bad row band [%d,%d) of %d", row_begin, row_end, th);
+int check_grid(const Band &b) {
+    MS_REQUIRE(b.tile_size > 0 && b.tw > 0 && b.th > 0, MS_ERR_INVALID_ARG, "isect: bad tile grid");
+    MS_REQUIRE((int64_t)b.tw * b.th < (1ll << 30), MS_ERR_TOO_LARGE, "isect: tile grid too large");
+    MS_REQUIRE(b.row_begin >= 0 && b.row_begin <= b.row_end && b.row_end <= b.th, MS_ERR_INVALID_ARG,
+               "isect: bad row band [%d,%d) of %d", b.row_begin, b.row_end, b.th);
     return MS_OK;
 }
 
@@ -2138,48 +2160,57 @@ int allow_big_lds(K kernel) {
 
 namespace {
 // per-tile prefix over the partial histograms -> tile_ranges, M, work lists
-int count_tail(const Plan &p, const Grid &g, char *ws, uint32_t *hist, uint32_t *count, int32_t *medium,
-               int32_t *large, int32_t *xl, const uint32_t *wg_on_grid, int n_wg, int32_t *tile_ranges,
-               int64_t *isect_info, int band_only, int64_t *info_mirror, hipStream_t stream, bool defer_total = false) {
-    ScanTotalArgs A{g, count, tile_ranges, medium, large, xl, wg_on_grid, n_wg, (int32_t *)(ws + p.off_redo_flag),
-                    (int32_t *)(ws + p.off_redo_count), band_only, isect_info, info_mirror, (int32_t *)(ws + p.off_order),
-                    (uint32_t *)wg_on_grid + kMaxG, nullptr, nullptr, 0u, nullptr, 0, nullptr, nullptr};
-    if (defer_total && p.T_local > 0) {
-        // the per-tile prefix over the partial rows alone: the total pass rides in the scatter launch (deferred_total)
-        A.ticket = nullptr;
-        if (p.T_local <= 4096)
-            hipLaunchKernelGGL(k_tile_scan_wg<16>, dim3((unsigned)ms::ceil_div(p.T_local, 16)), dim3(1024), 0, stream,
-                               p.G, p.T_local, hist, count, A);
-        else
-            hipLaunchKernelGGL(k_tile_scan_wg<64>, dim3((unsigned)ms::ceil_div(p.T_local, 64)), dim3(1024), 0, stream,
-                               p.G, p.T_local, hist, count, A);
-        MS_LAUNCH_CHECK();
-        return MS_OK;
-    }
-    if (p.T_local > 0) {
-        // (the last workgroup to arrive runs the total pass)
-        if (p.T_local <= 4096)
-            hipLaunchKernelGGL(k_tile_scan_wg<16>, dim3((unsigned)ms::ceil_div(p.T_local, 16)), dim3(1024), 0, stream,
-                               p.G, p.T_local, hist, count, A);
-        else {
-            // (and the total pass in a launch of its own: 17 us in two launches, 24 in one, on 8 160 tiles)
-            ScanTotalArgs A0 = A;
-            A0.ticket = nullptr;
-            hipLaunchKernelGGL(k_tile_scan_wg<64>, dim3((unsigned)ms::ceil_div(p.T_local, 64)), dim3(1024), 0, stream,
-                               p.G, p.T_local, hist, count, A0);
-            hipLaunchKernelGGL(k_tile_scan_total, dim3(1), dim3(1024), 0, stream, A0);
-        }
-    } else {
-        A.ticket = nullptr;
-        hipLaunchKernelGGL(k_tile_scan_total, dim3(1), dim3(1024), 0, stream, A);
-    }
+// WHICH instance of k_project_hist and k_isect_scatter a frame takes -- derived here and nowhere else, so that the count and the
+// emit of a frame cannot disagree.  (The count applies what only it knows to the mode first: no opacities, no reach masks;
+// no records, no lean frame.)
+struct KernelForm {
+    bool masks;    // reach masks: written by the count kernel, read back by the scatter
+    bool pack;     // block masks: entries carry the 2x2 half-tile blocks they reach
+    bool lean;     // LeanRecs instead of the projected arrays
+    bool lean12;   // ... and on plain bins of grids up to 255 tiles a side the 12-byte record with the mask in it
+};
+KernelForm kernel_form(const ms::BinMode &m, const Band &b) {
+    KernelForm f;
+    f.masks = m.reach_masks;
+    f.pack = m.block_masks && f.masks && (b.tile_size & 1) == 0 && b.N < (1ll << 28);
+    f.lean = m.lean && f.masks && b.tw <= 0xffff && b.th <= 0xffff && b.N < (1ll << 28);
+    f.lean12 = f.lean && !f.pack && b.tw <= 255 && b.th <= 255;
+    return f;
+}
+// (odd_cols / odd_rows: the half-tile grid has an odd number of columns / rows)
+Grid make_grid(const Band &b, const ms::BinMode &m, const KernelForm &f) {
+    return Grid{b.tile_size, b.tw, b.th, b.row_begin, b.row_end, f.pack ? 1 : 0, 2 * b.tw - (m.odd_cols ? 1 : 0), 2 * b.th - (m.odd_rows ? 1 : 0)};
+}
+
+// (what the total pass is handed, wherever it runs: no arrival ticket, no depth cut, no claimed rows -- the caller adds those)
+ScanTotalArgs scan_total_args(const Layout &L, const Grid &g, int n_wg, int32_t *tile_ranges, int band_only, int64_t *info,
+                              int64_t *info_mirror) {
+    return ScanTotalArgs{g, L.count, tile_ranges, L.medium, L.large, L.xl, L.on_grid, n_wg, L.redo_flag, L.redo_count,
+                         band_only, info, info_mirror, L.order, nullptr, nullptr, nullptr, 0u, nullptr, 0, nullptr, nullptr};
+}
+void launch_tile_scan(const Layout &L, const Schedule &s, const ScanTotalArgs &A, hipStream_t stream) {
+    if (s.T_local <= 4096)
+        hipLaunchKernelGGL(k_tile_scan_wg<16>, dim3((unsigned)ms::ceil_div(s.T_local, 16)), dim3(1024), 0, stream, s.G, s.T_local, L.hist, L.count, A);
+    else
+        hipLaunchKernelGGL(k_tile_scan_wg<64>, dim3((unsigned)ms::ceil_div(s.T_local, 64)), dim3(1024), 0, stream, s.G, s.T_local, L.hist, L.count, A);
+}
+int count_tail(const Layout &L, const Schedule &s, const Grid &g, int n_wg, int32_t *tile_ranges, int64_t *isect_info, int band_only,
+               int64_t *info_mirror, hipStream_t stream, bool defer_total = false) {
+    ScanTotalArgs A = scan_total_args(L, g, n_wg, tile_ranges, band_only, isect_info, info_mirror);
+    // Where the total pass runs.  A deferred one rides in the scatter launch (deferred_total): the per-tile prefix alone here.
+    // Else on grids up to 4 096 tiles the prefix kernel's last workgroup to arrive runs it (the ticket); on larger ones, and
+    // for an empty band, it is a launch of its own (17 us in two launches, 24 in one, on 8 160 tiles)
+    const bool in_scan = s.T_local > 0 && s.T_local <= 4096 && !defer_total;
+    if (in_scan) A.ticket = L.scan_ticket();
+    if (s.T_local > 0) launch_tile_scan(L, s, A, stream);
+    if (!in_scan && !(defer_total && s.T_local > 0)) hipLaunchKernelGGL(k_tile_scan_total, dim3(1), dim3(1024), 0, stream, A);
     MS_LAUNCH_CHECK();
     return MS_OK;
 }
 }  // namespace
 
-// How deep the lazily sorted fronts of a frame are and how their depth buckets are laid out (k_tile_front).  `lazy`: bits 1-2 = the front level the caller asked for.
-ms::FrontParams ms::front_params(int tile_size, int lazy, float depth_near, float depth_far, bool merged, bool split) {
+// How deep the lazily sorted fronts of a frame are and how their depth buckets are laid out (k_tile_front).
+ms::FrontParams ms::front_params(int tile_size, const ms::SortMode &sort, float depth_near, float depth_far, bool merged, bool split) {
     ms::FrontParams fp;
     // all surviving depths lie in the camera's (near, far): fixed order-preserving buckets
     fp.fixed_min = 0;
@@ -2198,12 +2229,12 @@ ms::FrontParams ms::front_params(int tile_size, int lazy, float depth_near, floa
     const int blocks_per_tile = ((tile_size + 15) / 16) * ((tile_size + 15) / 16);
     // split frames: 1280 of a 32-px bin's nearest entries saturate its four blocks on the BASELINE
     // scenes (1024: one bin of config 3 falls short; 2048: +9 us).  A caller that saw the clean-up pass
-    // run asks for deeper fronts (lazy bits 1-2: front level, x2 each, up to the LDS room).
+    // run asks for deeper fronts (the front level: x2 each, up to the LDS room).
     static const int front_env = [] { const char *e = getenv("MOJOSPLAT_FRONT_K"); return e ? atoi(e) : 0; }();
     // plain 32-px bins: 1536 (config 3: 2048 costs +5 us per frame, 1024 sends one bin to the clean-up pass)
     int front_k = split ? 1280 : blocks_per_tile == 4 ? 1536 : min(kFrontK * blocks_per_tile, 2048);
     if (front_env >= 256 && front_env <= kFrontCap && blocks_per_tile > 1) front_k = front_env;   // (measurements)
-    fp.front_k = min(front_k << ((lazy >> 1) & 3), kFrontCap);   // (3072: 1-3 % slower, no fewer clean-ups on the BASELINE scenes)
+    fp.front_k = min(front_k << sort.front_level, kFrontCap);  // (3072: 1-3 % slower, no fewer clean-ups on the BASELINE scenes)
     // LDS room for the selected keys: the front plus the bucket that completes it; the merged launch
     // keeps it small (2048 keys: 25 KB per workgroup, four 512-thread workgroups per CU)
     fp.front_cap = merged ? min(kFrontCap, max(2048, (fp.front_k * 4 / 3 + 511) & ~511)) : kFrontCap;
@@ -2211,45 +2242,37 @@ ms::FrontParams ms::front_params(int tile_size, int lazy, float depth_near, floa
 }
 
 // Where the lazy-sorting bookkeeping lives inside an isect workspace (for ms_render_fwd's rasteriser).
-void ms::isect_lazy_arrays(void *workspace, int64_t N, int tile_w, int tile_h, ms::LazyLists *out) {
-    Plan p;
-    make_plan(N, tile_w, tile_h, 0, tile_h, p);
-    char *ws = (char *)workspace;
-    out->front_count = (int32_t *)(ws + p.off_front);
-    out->redo_flag = (int32_t *)(ws + p.off_redo_flag);
-    out->redo_list = (int32_t *)(ws + p.off_redo_list);
-    out->redo_count = (int32_t *)(ws + p.off_redo_count);
-    out->front_threshold = kFrontK;
-    out->keys = nullptr;  // the caller knows where it put them
-    out->bin_more = nullptr;
-    out->bin_w = 0;
-    out->packed = 0;
-    out->row_lo = 0;
-    out->row_hi = 0x7fffffff;
-    out->redo_grid = 256;
-    out->redo_sort = 0;
-    out->cut_stamp = 0;   // (a depth-cut frame's caller sets the stamp, the cut-off buffers, the record's words and the log)
-    out->tau = (uint32_t *)(ws + p.off_tau);   // (buffer 0; buffer 1 follows T words on: the caller picks)
-    out->tau_next = nullptr;
-    out->has_far = (const uint32_t *)(ws + p.off_has_far);
-    out->lean = ws + p.off_lean;
-    out->n_lean = N;
-    out->cut_words = nullptr;
-    out->log_keys = nullptr;
-    out->far_cnt = (uint32_t *)(ws + p.off_far_seg);
-    out->far_cur = out->far_cnt + p.T;
-    out->far_start = out->far_cnt + 2 * (size_t)p.T;
-    out->cut_inputs = nullptr;
-    out->verdict = nullptr;
-    out->cut_inputs = nullptr;
+ms::LazyLists ms::isect_lazy_arrays(const ms::Band &band) {
+    const Layout L(band);
+    // (everything else stays zero: the caller knows where it put the keys; a split frame's caller adds the bins' fields, a
+    // depth-cut frame's the stamp, the cut-off buffers, the record's words and the log)
+    ms::LazyLists out{};
+    out.front_count = L.front_count;
+    out.redo_flag = L.redo_flag;
+    out.redo_list = L.redo_list;
+    out.redo_count = L.redo_count;
+    out.front_threshold = kFrontK;
+    out.row_hi = 0x7fffffff;
+    out.redo_grid = 256;
+    out.tau = L.cutoffs(0);   // (buffer 1 follows tw * th words on: the caller picks)
+    out.has_far = L.has_far;
+    out.lean = L.lean_recs;
+    out.n_lean = band.N;
+    out.far_cnt = L.far_seg;
+    out.far_cur = out.far_cnt + L.T;
+    out.far_start = out.far_cnt + 2 * L.T;
+    return out;
 }
 
-// Can a frame on this grid take the depth cut (12-byte box records, room for the cut-offs in the count kernel's LDS)?
-bool ms::depth_cut_fits(int64_t N, int tile_w, int tile_h) {
-    Plan p;
-    if (!make_plan(N, tile_w, tile_h, 0, tile_h, p)) return false;
-    return tile_w <= 255 && tile_h <= 255 && N > 0 && N < (1ll << 28) &&
-           p.lds_bytes + (size_t)p.T_local * 5 + 16 <= kMaxLds;
+// Can a frame on this grid take the depth cut (12-byte box records, room for the cut-offs of the WHOLE grid in the count
+// kernel's LDS, whatever the band)?
+bool ms::depth_cut_fits(const ms::Band &band) {
+    ms::Band whole = band;
+    whole.row_begin = 0;
+    whole.row_end = band.th;
+    const Schedule s = make_schedule(whole);
+    return band.tw <= 255 && band.th <= 255 && band.N > 0 && band.N < (1ll << 28) &&
+           s.lds_bytes + (size_t)s.T_local * 5 + 16 <= kMaxLds;
 }
 
 namespace {
@@ -2444,19 +2467,18 @@ int ms::far_regen(const ms::LazyLists &lazy, int tw, int n_tiles, int64_t cap, v
     MS_REQUIRE(lazy.cut_inputs && n_tiles <= kRegenMaxTiles, MS_ERR_INVALID_ARG, "far_regen: a depth-cut frame without its inputs");
     const ms::CutInputs &I = *lazy.cut_inputs;
     const int th_ = n_tiles / (tw > 0 ? tw : 1);
-    MS_REQUIRE(I.row_begin >= 0 && I.row_begin <= I.row_end && I.row_end <= th_, MS_ERR_INVALID_ARG, "far_regen: bad band");
+    const Band &b = I.band;
+    MS_REQUIRE(b.tw == tw && b.th == th_ && b.row_begin >= 0 && b.row_begin <= b.row_end && b.row_end <= th_, MS_ERR_INVALID_ARG, "far_regen: bad band");
     Candidates cand{nullptr, nullptr, 0, 0};
     if (I.band_cull) {   // the band's candidate list, where the frame's count launch left it
-        Plan p;
-        MS_REQUIRE(I.isect_workspace && make_plan(I.g.N, tw, th_, I.row_begin, I.row_end, p), MS_ERR_INVALID_ARG, "far_regen: a pre-culled band without its workspace");
-        const char *ws = (const char *)I.isect_workspace;
-        cand = Candidates{(const int32_t *)(ws + p.off_cand), (const int32_t *)(ws + p.off_cand_count), p.G, p.chunk};
+        MS_REQUIRE(b.ws && I.count.G > 0 && fits_lds(I.count), MS_ERR_INVALID_ARG, "far_regen: a pre-culled band without its workspace");
+        cand = Layout(b).candidates(I.count);
     }
     const RegenProject R{I.g.means3d, I.g.scales, I.g.quats, I.g.opacities, I.v.viewmat, I.g.colors, I.g.color_dtype == MS_COLOR_F16 ? 1 : 0,
                          ms::make_proj_params(I.v, 0.0f, I.g.scales_are_log, I.g.opacities != nullptr),
                          (float4 *)I.records,
                          // (the band's rows: the count kernel clamped every box to them, and the reach masks' bits count from there)
-                         Grid{I.tile_size, tw, th_, I.row_begin, I.row_end, 0, 0, 0}, cand};
+                         Grid{b.tile_size, tw, th_, b.row_begin, b.row_end, 0, 0, 0}, cand};
     // (empty launches on almost every frame -- every workgroup reads the redo count and leaves; the frame costs the same
     // whatever their number: pipeline.hip, ms_redo_grid)
     const unsigned grid = 512u;
@@ -2480,11 +2502,7 @@ int ms::far_regen(const ms::LazyLists &lazy, int tw, int n_tiles, int64_t cap, v
 }
 
 // The band's tiles, heaviest list first, as the count pass leaves them (order[0 .. band tiles), absolute tile ids).
-const int32_t *ms::isect_order_array(const void *workspace, int64_t N, int tile_w, int tile_h) {
-    Plan p;
-    make_plan(N, tile_w, tile_h, 0, tile_h, p);
-    return (const int32_t *)((const char *)workspace + p.off_order);
-}
+const int32_t *ms::isect_order_array(const ms::Band &band) { return Layout(band).order; }
 
 #ifdef MS_DIAG
 extern "C" int ms_diag_set_bin_stamps(void *device_buffer) {
@@ -2559,10 +2577,8 @@ extern "C" int ms_scene_prepare(int64_t N, const float *means3d, const float *sc
 }
 
 extern "C" size_t ms_isect_workspace_bytes(int64_t N, int tile_w, int tile_h) {
-    Plan p;
     if (tile_w <= 0 || tile_h <= 0 || (int64_t)tile_w * tile_h >= (1ll << 30)) return 0;
-    make_plan(N, tile_w, tile_h, 0, tile_h, p);
-    return p.total;
+    return Layout(Band{N, 0, tile_w, tile_h, 0, tile_h, nullptr, 0}).total;
 }
 
 extern "C" int ms_isect_tiles_count(int64_t N, const float *means2d, const int32_t *radii,
@@ -2571,40 +2587,27 @@ extern "C" int ms_isect_tiles_count(int64_t N, const float *means2d, const int32
                                     int32_t *tiles_per_gauss, int32_t *tile_ranges,
                                     int64_t *isect_info, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
+    const Band band{N, tile_size, tile_w, tile_h, row_begin, row_end, workspace, workspace_bytes};
     MS_REQUIRE(N >= 0, MS_ERR_INVALID_ARG, "isect_count: N < 0");
-    if (int rc = check_grid(tile_size, tile_w, tile_h, row_begin, row_end)) return rc;
+    if (int rc = check_grid(band)) return rc;
     MS_REQUIRE(workspace && tile_ranges && isect_info && (N == 0 || (means2d && radii)),
                MS_ERR_INVALID_ARG, "isect_count: null pointer");
     MS_REQUIRE(((uintptr_t)means2d & 7) == 0 && ((uintptr_t)radii & 7) == 0 && ((uintptr_t)tile_ranges & 7) == 0,
                MS_ERR_INVALID_ARG, "isect_count: means2d/radii/tile_ranges must be 8-byte aligned");
-    Plan p;
-    const bool fits = make_plan(N, tile_w, tile_h, row_begin, row_end, p);
-    MS_REQUIRE(fits, MS_ERR_TOO_LARGE,
-               "isect_count: band of %d tiles needs %zu B of LDS (max %zu); bin in row bands",
-               p.T_local, p.lds_bytes, kMaxLds);
-    MS_REQUIRE(workspace_bytes >= p.total, MS_ERR_WORKSPACE, "isect_count: workspace %zu < %zu",
-               workspace_bytes, p.total);
-    char *ws = (char *)workspace;
-    uint32_t *hist = (uint32_t *)(ws + p.off_hist);
-    uint32_t *count = (uint32_t *)(ws + p.off_count);
-    int32_t *medium = (int32_t *)(ws + p.off_medium);
-    int32_t *large = (int32_t *)(ws + p.off_large), *xl = (int32_t *)(ws + p.off_xl);
-    uint32_t *on_grid = (uint32_t *)(ws + p.off_on_grid);
+    const Schedule s = make_schedule(band);
+    const Layout L(band);
+    if (int rc = check_band(band, s, L, "isect_count")) return rc;
     const Grid g{tile_size, tile_w, tile_h, row_begin, row_end, 0, 0, 0};
 
-    if (p.T_local > 0) {
-        if (p.lds_bytes > 48 * 1024)
+    // (an empty band has nothing to histogram, but the frame-level on-grid count is still owed; an empty scene owes nothing)
+    if (s.T_local > 0 || N > 0) {
+        if (s.lds_bytes > 48 * 1024)
             if (int rc = allow_big_lds(k_isect_hist)) return rc;
-        hipLaunchKernelGGL(k_isect_hist, dim3(p.G), dim3(kHistThreads), p.lds_bytes, stream, N, means2d,
-                           radii, g, p.chunk, hist, tiles_per_gauss, on_grid);
-        MS_LAUNCH_CHECK();
-    } else if (N > 0) {  // empty band: nothing to histogram, but the frame-level on-grid count is still owed
-        hipLaunchKernelGGL(k_isect_hist, dim3(p.G), dim3(kHistThreads), p.lds_bytes, stream, N, means2d, radii, g,
-                           p.chunk, hist, tiles_per_gauss, on_grid);
+        hipLaunchKernelGGL(k_isect_hist, dim3(s.G), dim3(kHistThreads), s.lds_bytes, stream, N, means2d,
+                           radii, g, s.chunk, L.hist, tiles_per_gauss, L.on_grid);
         MS_LAUNCH_CHECK();
     }
-    return count_tail(p, g, ws, hist, count, medium, large, xl, on_grid, N > 0 ? p.G : 0, tile_ranges, isect_info,
-                      /*band_only=*/0, nullptr, stream);
+    return count_tail(L, s, g, N > 0 ? s.G : 0, tile_ranges, isect_info, /*band_only=*/0, nullptr, stream);
 }
 
 // Projection + tile counting in one pass over the Gaussians (what a frame starts with): the
@@ -2621,16 +2624,19 @@ extern "C" int ms_project_isect_count(int64_t N, const float *means3d, const flo
                                       void *stream_) {
     const ms::Gaussians g{N, means3d, scales, scales_are_log, quats, opacities, nullptr, 0, 0};
     const ms::View v{viewmat, fx, fy, cx, cy, W, H, eps2d, near_plane, far_plane};
-    return ms::project_isect_count(g, v, radius_clip, tile_size, row_begin, row_end, tight & 63, means2d, conics, depths, radii,
-                                   workspace, workspace_bytes, tile_ranges, isect_info, isect_info_mirror, nullptr, stream_, 0u);
+    // (the grid of a bad tile size is never looked at: the sizes are checked first)
+    const int tile_w = tile_size > 0 ? (W + tile_size - 1) / tile_size : 0, tile_h = tile_size > 0 ? (H + tile_size - 1) / tile_size : 0;
+    return ms::project_isect_count(g, v, radius_clip, ms::Band{N, tile_size, tile_w, tile_h, row_begin, row_end, workspace, workspace_bytes},
+                                   ms::decode_tight(tight & 63), means2d, conics, depths, radii, tile_ranges, isect_info,
+                                   isect_info_mirror, nullptr, stream_, 0u);
 }
 
-int ms::project_isect_count(const ms::Gaussians &gs, const ms::View &v, float radius_clip, int tile_size, int row_begin,
-                            int row_end, int tight, float *means2d, float *conics, float *depths, int32_t *radii,
-                            void *workspace, size_t workspace_bytes, int32_t *tile_ranges, int64_t *isect_info,
-                            int64_t *isect_info_mirror, void *raster_records, void *stream_, uint32_t cut_stamp,
-                            const float *block_bounds, int block_size) {
+int ms::project_isect_count(const ms::Gaussians &gs, const ms::View &v, float radius_clip, const ms::Band &band, ms::BinMode mode,
+                            float *means2d, float *conics, float *depths, int32_t *radii, int32_t *tile_ranges,
+                            int64_t *isect_info, int64_t *isect_info_mirror, void *raster_records, void *stream_,
+                            uint32_t cut_stamp, const float *block_bounds, int block_size, ms::Schedule *launched) {
     const int64_t N = gs.N;
+    const int tile_size = band.tile_size, tile_w = band.tw, tile_h = band.th;
     hipStream_t stream = (hipStream_t)stream_;
     const void *colors3 = raster_records ? gs.colors : nullptr;   // (read for the records alone)
     if (!gs.opacities || !colors3) raster_records = nullptr;
@@ -2640,61 +2646,49 @@ int ms::project_isect_count(const ms::Gaussians &gs, const ms::View &v, float ra
                    "project_isect_count: a prepared scene's block size must be a power of two >= 64 (got %d)", block_size);
         while ((1 << block_shift) < block_size) ++block_shift;
     }
-    MS_REQUIRE(N >= 0 && v.W > 0 && v.H > 0 && tile_size > 0 && v.fx != 0.f && v.fy != 0.f, MS_ERR_INVALID_ARG,
+    MS_REQUIRE(N >= 0 && band.N == N && v.W > 0 && v.H > 0 && tile_size > 0 && v.fx != 0.f && v.fy != 0.f, MS_ERR_INVALID_ARG,
                "project_isect_count: bad sizes / camera");
-    const int tile_w = (v.W + tile_size - 1) / tile_size, tile_h = (v.H + tile_size - 1) / tile_size;
-    if (int rc = check_grid(tile_size, tile_w, tile_h, row_begin, row_end)) return rc;
-    MS_REQUIRE(workspace && tile_ranges && isect_info &&
+    if (int rc = check_grid(band)) return rc;
+    MS_REQUIRE(band.ws && tile_ranges && isect_info &&
                    (N == 0 || (gs.means3d && gs.scales && gs.quats && v.viewmat && means2d && conics && depths && radii)),
                MS_ERR_INVALID_ARG, "project_isect_count: null pointer");
     MS_REQUIRE(((uintptr_t)gs.quats & 15) == 0 && ((uintptr_t)means2d & 7) == 0 && ((uintptr_t)radii & 7) == 0 &&
                    ((uintptr_t)tile_ranges & 7) == 0,
                MS_ERR_INVALID_ARG, "project_isect_count: quats 16-byte, means2d/radii/tile_ranges 8-byte aligned");
-    Plan p;
-    const bool fits = make_plan(N, tile_w, tile_h, row_begin, row_end, p);
-    MS_REQUIRE(fits, MS_ERR_TOO_LARGE, "project_isect_count: band of %d tiles needs %zu B of LDS (max %zu)",
-               p.T_local, p.lds_bytes, kMaxLds);
-    MS_REQUIRE(workspace_bytes >= p.total, MS_ERR_WORKSPACE, "project_isect_count: workspace %zu < %zu",
-               workspace_bytes, p.total);
-    char *ws = (char *)workspace;
-    uint32_t *hist = (uint32_t *)(ws + p.off_hist);
-    uint32_t *count = (uint32_t *)(ws + p.off_count);
-    int32_t *medium = (int32_t *)(ws + p.off_medium);
-    int32_t *large = (int32_t *)(ws + p.off_large), *xl = (int32_t *)(ws + p.off_xl);
-    uint32_t *on_grid = (uint32_t *)(ws + p.off_on_grid);
-    // block masks (bit 2): entries carry the 2x2 half-tile blocks they reach; bits 3 / 4: the half-tile
-    // grid has an odd number of columns / rows (2 tile_w - 1, 2 tile_h - 1)
-    const bool pack = (tight & 4) && (tight & 1) && gs.opacities && (tile_size & 1) == 0 && N < (1ll << 28);
-    const Grid g{tile_size, tile_w, tile_h, row_begin, row_end, pack ? 1 : 0, 2 * tile_w - ((tight >> 3) & 1),
-                 2 * tile_h - ((tight >> 4) & 1)};
-    unsigned long long *masks = ((tight & 1) && gs.opacities) ? (unsigned long long *)(ws + p.off_mask) : nullptr;
+    const Schedule p = make_schedule(band);
+    const Layout L(band);
+    if (int rc = check_band(band, p, L, "project_isect_count")) return rc;
+    if (launched) *launched = p;
+    // what only the count knows: without opacities there is nothing to bound a reach by, without records no lean frame
+    if (!gs.opacities) mode.reach_masks = false;
+    if (!raster_records) mode.lean = false;
+    if (N >= (1ll << 28)) mode.band_cull = false;   // (the candidates' gather indexes with 32-bit byte offsets)
+    const KernelForm form = kernel_form(mode, band);
+    const bool pack = form.pack, lean = form.lean, lean12 = form.lean12;
+    const Grid g = make_grid(band, mode, form);
+    unsigned long long *masks = form.masks ? L.masks : nullptr;
     const ms::ProjParams P = ms::make_proj_params(v, radius_clip, gs.scales_are_log, gs.opacities != nullptr);
-    // bit 5 of `tight`: the band is a rank's share of a frame -- pre-cull the Gaussians that cannot reach it
+    // the band is a rank's share of a frame: pre-cull the Gaussians that cannot reach it
     Candidates cand{nullptr, nullptr, 0, 0};
-    if ((tight & kBandCull) && N >= (1ll << 28)) tight &= ~kBandCull;   // (the candidates' gather indexes with 32-bit byte offsets)
-    if ((tight & kBandCull) && N > 0) {
-        int32_t *seg_count = (int32_t *)(ws + p.off_cand_count);
+    if (mode.band_cull && N > 0) {
         hipLaunchKernelGGL(block_bounds ? k_band_precull<true> : k_band_precull<false>, dim3(p.G), dim3(kHistThreads), 0, stream, N,
-                           gs.means3d, gs.scales, v.viewmat, P, (float)(row_begin * tile_size) - 1.0f, (float)(row_end * tile_size) + 1.0f,
-                           p.chunk, (int32_t *)(ws + p.off_cand), seg_count, block_bounds, block_shift);
+                           gs.means3d, gs.scales, v.viewmat, P, (float)(band.row_begin * tile_size) - 1.0f, (float)(band.row_end * tile_size) + 1.0f,
+                           p.chunk, L.cand_ids, L.cand_count, block_bounds, block_shift);
         MS_LAUNCH_CHECK();
-        cand = Candidates{(const int32_t *)(ws + p.off_cand), seg_count, p.G, p.chunk};
+        cand = L.candidates(p);
     }
-    // claimed rows (round 6; ms::kTightClaimed, set by ms_render_fwd for sync-free frames whose total pass rides in the scatter
-    // launch): no prefix kernel behind this one (profiles/r06_claimed_rows.md)
+    // claimed rows (set by ms_render_fwd for sync-free frames whose total pass rides in the scatter launch): no prefix
+    // kernel behind this one (profiles/r06_claimed_rows.md)
     static std::atomic<unsigned long long> claim_stamps{0x5ca1ab1e00000000ull};   // (never a value fresh memory is likely to hold)
-    const bool claimed = (tight & ms::kTightClaimed) && (tight & kDeferTotal) && p.T_local > 0;
+    const bool claimed = mode.claimed && mode.defer_total && p.T_local > 0;
     {   // also for N == 0 (one workgroup that walks nothing): the histogram row and the on-grid slot the
         // scans read must exist
-        // lean frame: LeanRecs instead of the projected arrays (the caller vouches that nobody reads those)
-        const bool lean = (tight & kLean) && raster_records && masks && tile_w <= 0xffff && tile_h <= 0xffff && N < (1ll << 28);
-        const bool lean12 = lean && !pack && tile_w <= 255 && tile_h <= 255;
         auto kernel = pack ? (lean ? k_project_hist<true, 1> : k_project_hist<true, 0>)
                            : (lean12 ? (cut_stamp ? k_project_hist<false, 2, true> : k_project_hist<false, 2>)
                                      : lean ? k_project_hist<false, 1> : k_project_hist<false, 0>);
         // depth-cut frame: per-tile cut-offs beside the counters (the sort kernel of the previous frame left them)
-        const bool cut = cut_stamp != 0u;   // (bit 9 of `tight`: which of the two cut-off buffers to read)
-        MS_REQUIRE(!cut || (lean12 && (tight & kDeferTotal)), MS_ERR_INVALID_ARG,
+        const bool cut = cut_stamp != 0u;
+        MS_REQUIRE(!cut || (lean12 && mode.defer_total), MS_ERR_INVALID_ARG,
                    "project_isect_count: a depth-cut frame must be a lean sync-free frame on plain bins");
         size_t lds = p.lds_bytes + (cut ? (size_t)p.T_local * 5 + 16 : 0);
         MS_REQUIRE(lds <= kMaxLds, MS_ERR_TOO_LARGE, "project_isect_count: %d tiles with cut-offs need %zu B of LDS", p.T_local, lds);
@@ -2706,79 +2700,74 @@ int ms::project_isect_count(const ms::Gaussians &gs, const ms::View &v, float ra
         if (lds > 48 * 1024)
             if (int rc = allow_big_lds(kernel)) return rc;
         hipLaunchKernelGGL(kernel, dim3(p.G), dim3(kHistThreads), lds, stream, N, gs.means3d, gs.scales,
-                           gs.quats, gs.opacities, v.viewmat, P, g, p.chunk, means2d, conics, depths, radii, hist, on_grid, masks,
+                           gs.quats, gs.opacities, v.viewmat, P, g, p.chunk, means2d, conics, depths, radii, L.hist, L.on_grid, masks,
                            colors3, gs.color_dtype == MS_COLOR_F16 ? 1 : 0, (float4 *)raster_records, cand,
-                           (LeanRec *)(ws + p.off_lean), (uint32_t *)(ws + p.off_depth_wg),
-                           cut ? (const uint32_t *)(ws + p.off_tau) + (size_t)((tight >> 9) & 1) * p.T : nullptr, (uint32_t *)(ws + p.off_wg_far),
-                           (uint32_t *)(ws + p.off_has_far), cut_stamp, (LeanRec *)(ws + p.off_near), (tight & ms::kTightKeepArrays) ? 1 : 0, p.near_cap,
-                           big_q_off, big_q_cap, claimed ? (uint32_t *)(ws + p.off_xtot) : nullptr,
-                           // (the flag: two words of the 256-byte block the clean-up counts start -- words 0-2 -- 8-byte aligned)
-                           (unsigned long long *)(ws + p.off_redo_count + 64), claimed ? ++claim_stamps : 0ull);
+                           L.lean_recs, L.depth_wg, cut ? (const uint32_t *)L.cutoffs(mode.cut_in) : nullptr, L.wg_far,
+                           L.has_far, cut_stamp, L.near_recs, mode.keep_arrays ? 1 : 0, p.near_cap,
+                           big_q_off, big_q_cap, claimed ? L.claims : nullptr, L.claim_flag(), claimed ? ++claim_stamps : 0ull);
         MS_LAUNCH_CHECK();
     }
     if (claimed) return MS_OK;   // (the rows are exclusive offsets already, `count` the tile counts: no prefix kernel)
-    return count_tail(p, g, ws, hist, count, medium, large, xl, on_grid, p.G, tile_ranges, isect_info,
-                      (tight & 2) ? 1 : 0, isect_info_mirror, stream, (tight & kDeferTotal) != 0);
+    return count_tail(L, p, g, p.G, tile_ranges, isect_info, mode.band_only ? 1 : 0, isect_info_mirror, stream, mode.defer_total);
 }
 
 namespace {
 // Shared by the exact emit (host knows M and the class counts) and the speculative one (it does
 // not: `info_dev` is the count pass's device record, `cap` the capacity of the key/id buffers).
-int emit_impl(int64_t N, const float *means2d, const int32_t *radii, const float *depths, int tight, int lazy,
-              float depth_near, float depth_far, int tile_size,
-              int tile_w, int tile_h, int row_begin, int row_end, void *workspace, size_t workspace_bytes,
-              const int32_t *tile_ranges, const int64_t *host_info, const int64_t *info_dev, int64_t cap,
-              uint64_t *sort_keys, uint64_t *sort_tmp, int32_t *flatten_ids, int64_t *isect_ids,
-              hipStream_t stream, const ms::BlockLists *blocks = nullptr, const ms::DeferredTotal *defer = nullptr,
-              ms::FusedSort *fuse = nullptr) {
+// The buffers of an emit.  host_info: the exact emit's size record -- or, beside info_dev, the previous frame's (or null)
+struct EmitBuffers {
+    const float *means2d;
+    const int32_t *radii, *tile_ranges;
+    const float *depths;
+    const int64_t *host_info, *info_dev;
+    int64_t cap;
+    uint64_t *sort_keys, *sort_tmp;
+    int32_t *flatten_ids;
+    int64_t *isect_ids;
+    const ms::BlockLists *blocks;
+    const ms::DeferredTotal *defer;
+    ms::FusedSort *fuse;
+};
+int emit_impl(const Band &band, const ms::BinMode &bin, const ms::SortMode &sort, float depth_near, float depth_far,
+              const EmitBuffers &B, hipStream_t stream) {
+    const auto [means2d, radii, tile_ranges, depths, host_info, info_dev, cap, sort_keys, sort_tmp, flatten_ids, isect_ids, blocks, defer, fuse] = B;
+    const int64_t N = band.N;
+    const int tile_size = band.tile_size, tile_w = band.tw, tile_h = band.th, row_begin = band.row_begin;
+    const bool lazy = sort.on;
     if (fuse) fuse->taken = 0;
     const ms::BlockLists bl = blocks ? *blocks : ms::BlockLists{nullptr, nullptr, nullptr, 0, 0};
     const uint32_t cut_stamp = defer ? defer->cut_stamp : 0u;   // != 0: a depth-cut frame (k_project_hist)
-    // bits 4-5 of `lazy` (ms_render_fwd only): the merged sort launch leaves the NEXT frame's cut-offs in buffer (lazy >> 4) & 1;
-    // a depth-cut frame reads its own from the other one
-    const int tau_out = (lazy >> 4) & 1;
-    const bool write_tau = (lazy & 32) != 0;
-    Plan p;
-    const bool fits = make_plan(N, tile_w, tile_h, row_begin, row_end, p);
-    MS_REQUIRE(fits, MS_ERR_TOO_LARGE, "isect_emit: band too large for LDS");
-    MS_REQUIRE(workspace_bytes >= p.total, MS_ERR_WORKSPACE, "isect_emit: workspace %zu < %zu",
-               workspace_bytes, p.total);
-    char *ws = (char *)workspace;
-    const uint32_t *hist = (const uint32_t *)(ws + p.off_hist);
-    const int32_t *medium = (const int32_t *)(ws + p.off_medium);
-    const int32_t *large = (const int32_t *)(ws + p.off_large), *xl = (const int32_t *)(ws + p.off_xl);
-    const bool pack = (tight & 4) && (tight & 1) && (tile_size & 1) == 0 && N < (1ll << 28);
-    const Grid g{tile_size, tile_w, tile_h, row_begin, row_end, pack ? 1 : 0, 2 * tile_w - ((tight >> 3) & 1),
-                 2 * tile_h - ((tight >> 4) & 1)};
-    const unsigned long long *masks = (tight & 1) ? (const unsigned long long *)(ws + p.off_mask) : nullptr;
+    const Schedule p = make_schedule(band);
+    const Layout ws(band);
+    if (int rc = check_band(band, p, ws, "isect_emit")) return rc;
+    const int T = tile_w * tile_h;
+    const int32_t *medium = ws.medium, *large = ws.large, *xl = ws.xl;
+    const KernelForm form = kernel_form(bin, band);
+    const bool pack = form.pack, lean = form.lean, lean12 = form.lean12;
+    const Grid g = make_grid(band, bin, form);
+    const unsigned long long *masks = form.masks ? ws.masks : nullptr;
+    // the cut-offs a depth-cut frame reads are in the buffer its sort launch does not write
+    const uint32_t *tau_now = ws.cutoffs(1 - sort.cut_out);
+    uint32_t *tau_next = sort.write_cutoffs ? ws.cutoffs(sort.cut_out) : nullptr;
     const bool spec = info_dev != nullptr;
     const int64_t max_count = spec ? 0 : host_info[1], n_medium = spec ? 0 : host_info[2],
                   n_large = spec ? 0 : host_info[3], n_xl = spec ? 0 : host_info[4];
 
     {
-        const bool lean = (tight & kLean) && masks && tile_w <= 0xffff && tile_h <= 0xffff && N < (1ll << 28);
-        const bool lean12 = lean && !pack && tile_w <= 255 && tile_h <= 255;
         const bool deferred = defer && p.T_local > 0;
         ScanTotalArgs A{};
+        if (deferred) A = scan_total_args(ws, g, p.G, const_cast<int32_t *>(tile_ranges), defer->band_only, defer->info, defer->info_mirror);
         // (claimed rows: the count pass of this frame claimed its rows per XCD -- the cursors of either scatter form add the
         // stretches of the XCDs before the workgroup's own)
-        const uint32_t *xtot = (tight & ms::kTightClaimed) && p.T_local > 0 ? (const uint32_t *)(ws + p.off_xtot) : nullptr;
-        A.xtot = xtot;
-        if (deferred) {
-            A = ScanTotalArgs{g, (const uint32_t *)(ws + p.off_count), const_cast<int32_t *>(tile_ranges), (int32_t *)(ws + p.off_medium),
-                              (int32_t *)(ws + p.off_large), (int32_t *)(ws + p.off_xl), (const uint32_t *)(ws + p.off_on_grid), p.G,
-                              (int32_t *)(ws + p.off_redo_flag), (int32_t *)(ws + p.off_redo_count), defer->band_only,
-                              defer->info, defer->info_mirror, (int32_t *)(ws + p.off_order), nullptr,
-                              nullptr, nullptr, 0u, nullptr, 0, nullptr, xtot};
-            if (defer->cut_stamp) {
-                MS_REQUIRE(lean12 && lazy, MS_ERR_INVALID_ARG, "isect emit: a depth-cut frame must be a lean, lazily sorted frame on plain bins");
-                A.wg_far = (const uint32_t *)(ws + p.off_wg_far);
-                A.tau = (const uint32_t *)(ws + p.off_tau) + (size_t)(1 - tau_out) * p.T;
-                A.cut_stamp = defer->cut_stamp;
-                A.far_zero = (uint32_t *)(ws + p.off_far_seg);
-                A.near_recs = (const LeanRec *)(ws + p.off_near);
-                A.near_cap = p.near_cap;
-            }
+        A.xtot = bin.claimed && p.T_local > 0 ? ws.claims : nullptr;
+        if (deferred && defer->cut_stamp) {
+            MS_REQUIRE(lean12 && lazy, MS_ERR_INVALID_ARG, "isect emit: a depth-cut frame must be a lean, lazily sorted frame on plain bins");
+            A.wg_far = ws.wg_far;
+            A.tau = tau_now;
+            A.cut_stamp = defer->cut_stamp;
+            A.far_zero = ws.far_seg;
+            A.near_recs = ws.near_recs;
+            A.near_cap = p.near_cap;
         }
         size_t scatter_lds = p.lds_bytes + (A.cut_stamp ? (size_t)p.T_local * 4 + 16 : 0);
         const unsigned int big_q_off = (unsigned int)ms::align_up(scatter_lds, 16);
@@ -2795,11 +2784,10 @@ int emit_impl(int64_t N, const float *means2d, const int32_t *radii, const float
         if (scatter_lds > 48 * 1024)
             if (int rc = allow_big_lds(kernel)) return rc;
         hipLaunchKernelGGL(kernel, dim3(p.G + (deferred ? 2 : 0)), dim3(kHistThreads), scatter_lds, stream, N, means2d, radii, depths, masks,
-                           (const LeanRec *)(ws + p.off_lean), g, p.chunk, hist, tile_ranges, cap, sort_keys,
+                           ws.lean_recs, g, p.chunk, ws.hist, tile_ranges, cap, sort_keys,
                            // (a lean frame's count kernel has left the per-workgroup depth ranges already)
-                           lazy && !lean ? (uint32_t *)(ws + p.off_depth_wg) : nullptr,
-                           (tight & kBandCull) ? Candidates{(const int32_t *)(ws + p.off_cand), (const int32_t *)(ws + p.off_cand_count), p.G, p.chunk}
-                                               : Candidates{nullptr, nullptr, 0, 0}, p.G, A, big_q_off, big_q_cap);
+                           lazy && !lean ? ws.depth_wg : nullptr,
+                           bin.band_cull ? ws.candidates(p) : Candidates{nullptr, nullptr, 0, 0}, p.G, A, big_q_off, big_q_cap);
         MS_LAUNCH_CHECK();
         // the size record is complete once the scatter launch is: the caller's hand-off event goes here
         if (deferred && defer->sync_event) MS_HIP(hipEventRecord((hipEvent_t)defer->sync_event, stream));
@@ -2822,9 +2810,9 @@ int emit_impl(int64_t N, const float *means2d, const int32_t *radii, const float
         // launches, for measurements)
         static const bool merged_env = [] { const char *e = getenv("MOJOSPLAT_MERGED_SORT"); return !e || atoi(e) != 0; }();
         // no tile beyond the small class (known on the exact path; the caller's bet on a speculative frame,
-        // bit 3 of `lazy`): the 256-thread small-sort launch alone -- 7.8 us at config 2 against 14.6 for the merged
+        // SortMode::light_bet): the 256-thread small-sort launch alone -- 7.8 us at config 2 against 14.6 for the merged
         // launch, whose 512-thread workgroups are sized for the fronts
-        const bool no_heavy = !bl.block_ids && (spec ? (lazy & 8) != 0 : n_medium + n_large + n_xl == 0);
+        const bool no_heavy = !bl.block_ids && (spec ? sort.light_bet : n_medium + n_large + n_xl == 0);
         const bool merged = merged_env && !bl.block_ids && p.T_local > 0 && !no_heavy;
         if (!no_heavy && (merged || spec || n_medium + n_large + n_xl > 0)) {
             auto front = bl.block_ids ? k_tile_front<true, false> : merged ? k_tile_front<false, true> : k_tile_front<false, false>;
@@ -2837,33 +2825,26 @@ int emit_impl(int64_t N, const float *means2d, const int32_t *radii, const float
                 const int64_t prev_heavy = host_info[2] + host_info[3] + host_info[4];
                 guess = prev_heavy > 0 ? prev_heavy + prev_heavy / 4 + 16 : 1024;
             }
-            const unsigned grid = spec ? (unsigned)min((int64_t)min(p.T, 1024), guess)
+            const unsigned grid = spec ? (unsigned)min((int64_t)min(T, 1024), guess)
                                        : (unsigned)(heavy < 1024 ? heavy : 1024);
-            const ms::FrontParams fp = ms::front_params(tile_size, lazy, depth_near, depth_far, merged, bl.block_ids != nullptr);
-            const uint32_t fixed_min = fp.fixed_min;
-            const int fixed_shift = fp.fixed_shift, front_k = fp.front_k, front_cap = fp.front_cap;
+            const ms::FrontParams fp = ms::front_params(tile_size, sort, depth_near, depth_far, merged, bl.block_ids != nullptr);
             // The rasteriser sorts each bin in the workgroup that rasterises it (rasterize.hip, k_sort_rasterize): the merged
             // launch on 32-px bins at the default front depth (2048 keys of LDS room) is left to it, with what it would have taken
-            if (fuse && merged && spec && tile_size == 32 && front_cap <= 2048) {
-                *fuse = ms::FusedSort{1, fp, (const uint32_t *)(ws + p.off_depth_wg), p.G, (const int32_t *)(ws + p.off_order), p.T_local,
-                                      write_tau ? (uint32_t *)(ws + p.off_tau) + (size_t)tau_out * p.T : nullptr,
-                                      (const uint32_t *)(ws + p.off_tau) + (size_t)(1 - tau_out) * p.T, (const uint32_t *)(ws + p.off_has_far),
-                                      cut_stamp, cap, sort_keys, flatten_ids, (int32_t *)(ws + p.off_front)};
+            if (fuse && merged && spec && tile_size == 32 && fp.front_cap <= 2048) {
+                *fuse = ms::FusedSort{1, fp, ws.depth_wg, p.G, ws.order, p.T_local, tau_next, tau_now, ws.has_far,
+                                      cut_stamp, cap, sort_keys, flatten_ids, ws.front_count};
                 return MS_OK;
             }
-            size_t front_lds = kFrontLds - (size_t)(kFrontCap - front_cap) * 8;
+            size_t front_lds = kFrontLds - (size_t)(kFrontCap - fp.front_cap) * 8;
             // (merged launch: room for eight waves' private sorts of light lists)
             const bool light = merged;
             if (light && front_lds < 8 * SortCfg<64, kLightCap / 64>::LDS) front_lds = 8 * SortCfg<64, kLightCap / 64>::LDS;
             hipLaunchKernelGGL(front, dim3(merged ? (unsigned)p.T_local : grid), dim3(kFrontThreads), front_lds, stream,
                                medium, large, xl,
                                spec ? info_dev : nullptr, (int)n_medium, (int)n_large, (int)n_xl, tile_ranges,
-                               sort_keys, flatten_ids, (int32_t *)(ws + p.off_front), cap, fixed_min, fixed_shift,
-                               front_k, bl, tile_w, (const uint32_t *)(ws + p.off_depth_wg), p.G,
-                               (const int32_t *)(ws + p.off_order), p.T_local, front_cap,
-                               light ? (const uint32_t *)(ws + p.off_on_grid) + kMaxG + 1 : nullptr,
-                               merged && write_tau ? (uint32_t *)(ws + p.off_tau) + (size_t)tau_out * p.T : nullptr,
-                               (const uint32_t *)(ws + p.off_tau) + (size_t)(1 - tau_out) * p.T, (const uint32_t *)(ws + p.off_has_far), cut_stamp);
+                               sort_keys, flatten_ids, ws.front_count, cap, fp.fixed_min, fp.fixed_shift,
+                               fp.front_k, bl, tile_w, ws.depth_wg, p.G, ws.order, p.T_local, fp.front_cap,
+                               light ? ws.light_count() : nullptr, merged ? tau_next : nullptr, tau_now, ws.has_far, cut_stamp);
             MS_LAUNCH_CHECK();
         }
         if (merged) return MS_OK;
@@ -2879,7 +2860,7 @@ int emit_impl(int64_t N, const float *means2d, const int32_t *radii, const float
     const size_t medium_lds = SortCfg<1024, 8>::LDS, large_lds = SortCfg<1024, 16>::LDS;
     if (spec || n_medium > 0) {
         if (int rc = allow_big_lds(k_tile_sort_list<8>)) return rc;
-        const unsigned grid = spec ? (unsigned)min(p.T, 2048) : (unsigned)n_medium;
+        const unsigned grid = spec ? (unsigned)min(T, 2048) : (unsigned)n_medium;
         hipLaunchKernelGGL(k_tile_sort_list<8>, dim3(grid), dim3(1024), medium_lds, big, medium, tile_ranges,
                            sort_keys, flatten_ids, isect_ids, spec ? info_dev + 2 : nullptr, (int)n_medium, cap);
         MS_LAUNCH_CHECK();
@@ -2921,6 +2902,7 @@ int emit_impl(int64_t N, const float *means2d, const int32_t *radii, const float
 }
 }  // namespace
 
+// The C emits: mask the caller's words, decode them, forward.
 extern "C" int ms_isect_tiles_emit(int64_t N, const float *means2d, const int32_t *radii,
                                    const float *depths, int tile_size, int tile_w, int tile_h,
                                    int row_begin, int row_end, void *workspace,
@@ -2929,19 +2911,9 @@ extern "C" int ms_isect_tiles_emit(int64_t N, const float *means2d, const int32_
                                    float depth_far, uint64_t *sort_keys,
                                    uint64_t *sort_tmp, int32_t *flatten_ids, int64_t *isect_ids,
                                    void *stream_) {
-    MS_REQUIRE(N >= 0 && host_info, MS_ERR_INVALID_ARG, "isect_emit: bad N / host_info");
-    if (int rc = check_grid(tile_size, tile_w, tile_h, row_begin, row_end)) return rc;
-    const int64_t M = host_info[0], n_xl = host_info[4];
-    MS_REQUIRE(M >= 0 && M <= 0x7fffffffll, MS_ERR_TOO_LARGE,
-               "isect_emit: %lld intersections do not fit int32 indices", (long long)M);
-    if (M == 0) return MS_OK;
-    MS_REQUIRE(workspace && tile_ranges && means2d && radii && depths && sort_keys && flatten_ids,
-               MS_ERR_INVALID_ARG, "isect_emit: null pointer");
-    MS_REQUIRE(n_xl == 0 || sort_tmp || lazy, MS_ERR_INVALID_ARG, "isect_emit: sort_tmp required (XL tiles)");
-    MS_REQUIRE(!lazy || !isect_ids, MS_ERR_INVALID_ARG, "isect_emit: lazy lists carry no isect_ids");
-    return emit_impl(N, means2d, radii, depths, tight & 63, lazy & 15, depth_near, depth_far, tile_size, tile_w, tile_h,
-                     row_begin, row_end, workspace, workspace_bytes, tile_ranges, host_info, nullptr, M, sort_keys, sort_tmp,
-                     flatten_ids, isect_ids, (hipStream_t)stream_);
+    return ms::isect_emit_exact(Band{N, tile_size, tile_w, tile_h, row_begin, row_end, workspace, workspace_bytes},
+                                means2d, radii, depths, tile_ranges, host_info, ms::decode_tight(tight & 63),
+                                ms::decode_lazy(lazy & 15), depth_near, depth_far, sort_keys, sort_tmp, flatten_ids, stream_, isect_ids);
 }
 
 extern "C" int ms_isect_tiles_emit_speculative(int64_t N, const float *means2d, const int32_t *radii,
@@ -2952,64 +2924,61 @@ extern "C" int ms_isect_tiles_emit_speculative(int64_t N, const float *means2d, 
                                                const int64_t *prev_info_host, int tight, int lazy,
                                                float depth_near, float depth_far, uint64_t *sort_keys,
                                                int32_t *flatten_ids, void *stream_) {
-    MS_REQUIRE(N >= 0 && isect_info_dev && capacity > 0 && capacity <= 0x7fffffffll, MS_ERR_INVALID_ARG,
-               "isect_emit_speculative: bad N / info / capacity");
-    if (int rc = check_grid(tile_size, tile_w, tile_h, row_begin, row_end)) return rc;
-    MS_REQUIRE(workspace && tile_ranges && means2d && radii && depths && sort_keys && flatten_ids,
-               MS_ERR_INVALID_ARG, "isect_emit_speculative: null pointer");
-    return emit_impl(N, means2d, radii, depths, tight & 63, lazy & 15, depth_near, depth_far, tile_size, tile_w, tile_h,
-                     row_begin, row_end, workspace, workspace_bytes, tile_ranges, prev_info_host, isect_info_dev, capacity,
-                     sort_keys, nullptr, flatten_ids, nullptr, (hipStream_t)stream_);
+    return ms::isect_emit_speculative(Band{N, tile_size, tile_w, tile_h, row_begin, row_end, workspace, workspace_bytes},
+                                      means2d, radii, depths, tile_ranges, isect_info_dev, capacity, prev_info_host,
+                                      ms::decode_tight(tight & 63), ms::decode_lazy(lazy & 15), depth_near, depth_far, sort_keys,
+                                      flatten_ids, nullptr, stream_, nullptr);
 }
 
-int ms::isect_emit_speculative(int64_t N, const float *means2d, const int32_t *radii, const float *depths,
-                               int tile_size, int tile_w, int tile_h, int row_begin, int row_end, void *workspace,
-                               size_t workspace_bytes, const int32_t *tile_ranges, const int64_t *isect_info_dev,
-                               int64_t capacity, const int64_t *prev_info_host, int tight, int lazy, float depth_near,
-                               float depth_far, uint64_t *sort_keys, int32_t *flatten_ids,
-                               const ms::DeferredTotal *defer, void *stream_, ms::FusedSort *fuse) {
-    MS_REQUIRE(N >= 0 && isect_info_dev && capacity > 0 && capacity <= 0x7fffffffll, MS_ERR_INVALID_ARG,
+int ms::isect_emit_speculative(const ms::Band &band, const float *means2d, const int32_t *radii, const float *depths, const int32_t *tile_ranges,
+                               const int64_t *isect_info_dev, int64_t capacity, const int64_t *prev_info_host,
+                               const ms::BinMode &bin, const ms::SortMode &sort, float depth_near, float depth_far,
+                               uint64_t *sort_keys, int32_t *flatten_ids, const ms::DeferredTotal *defer, void *stream_,
+                               ms::FusedSort *fuse) {
+    MS_REQUIRE(band.N >= 0 && isect_info_dev && capacity > 0 && capacity <= 0x7fffffffll, MS_ERR_INVALID_ARG,
                "isect_emit_speculative: bad N / info / capacity");
-    if (int rc = check_grid(tile_size, tile_w, tile_h, row_begin, row_end)) return rc;
-    MS_REQUIRE(workspace && tile_ranges && means2d && radii && depths && sort_keys && flatten_ids,
+    if (int rc = check_grid(band)) return rc;
+    MS_REQUIRE(band.ws && tile_ranges && means2d && radii && depths && sort_keys && flatten_ids,
                MS_ERR_INVALID_ARG, "isect_emit_speculative: null pointer");
-    return emit_impl(N, means2d, radii, depths, tight, lazy, depth_near, depth_far, tile_size, tile_w, tile_h,
-                     row_begin, row_end, workspace, workspace_bytes, tile_ranges, prev_info_host, isect_info_dev, capacity,
-                     sort_keys, nullptr, flatten_ids, nullptr, (hipStream_t)stream_, nullptr, defer, fuse);
+    return emit_impl(band, bin, sort, depth_near, depth_far,
+                     EmitBuffers{means2d, radii, tile_ranges, depths, prev_info_host, isect_info_dev, capacity, sort_keys, nullptr, flatten_ids, nullptr,
+                                 nullptr, defer, fuse},
+                     (hipStream_t)stream_);
 }
 
-int ms::isect_emit_exact(int64_t N, const float *means2d, const int32_t *radii, const float *depths, int tile_size,
-                         int tile_w, int tile_h, int row_begin, int row_end, void *workspace, size_t workspace_bytes,
-                         const int32_t *tile_ranges, const int64_t *host_info, int tight, int lazy, float depth_near,
-                         float depth_far, uint64_t *sort_keys, uint64_t *sort_tmp, int32_t *flatten_ids, void *stream_) {
-    MS_REQUIRE(N >= 0 && host_info, MS_ERR_INVALID_ARG, "isect_emit: bad N / host_info");
-    if (int rc = check_grid(tile_size, tile_w, tile_h, row_begin, row_end)) return rc;
+int ms::isect_emit_exact(const ms::Band &band, const float *means2d, const int32_t *radii, const float *depths, const int32_t *tile_ranges, const int64_t *host_info,
+                         const ms::BinMode &bin, const ms::SortMode &sort, float depth_near, float depth_far,
+                         uint64_t *sort_keys, uint64_t *sort_tmp, int32_t *flatten_ids, void *stream_, int64_t *isect_ids) {
+    MS_REQUIRE(band.N >= 0 && host_info, MS_ERR_INVALID_ARG, "isect_emit: bad N / host_info");
+    if (int rc = check_grid(band)) return rc;
     const int64_t M = host_info[0], n_xl = host_info[4];
     MS_REQUIRE(M >= 0 && M <= 0x7fffffffll, MS_ERR_TOO_LARGE,
                "isect_emit: %lld intersections do not fit int32 indices", (long long)M);
     if (M == 0) return MS_OK;
-    MS_REQUIRE(workspace && tile_ranges && means2d && radii && depths && sort_keys && flatten_ids,
+    MS_REQUIRE(band.ws && tile_ranges && means2d && radii && depths && sort_keys && flatten_ids,
                MS_ERR_INVALID_ARG, "isect_emit: null pointer");
-    MS_REQUIRE(n_xl == 0 || sort_tmp || lazy, MS_ERR_INVALID_ARG, "isect_emit: sort_tmp required (XL tiles)");
-    return emit_impl(N, means2d, radii, depths, tight, lazy, depth_near, depth_far, tile_size, tile_w, tile_h,
-                     row_begin, row_end, workspace, workspace_bytes, tile_ranges, host_info, nullptr, M, sort_keys, sort_tmp,
-                     flatten_ids, nullptr, (hipStream_t)stream_);
+    MS_REQUIRE(n_xl == 0 || sort_tmp || sort.on, MS_ERR_INVALID_ARG, "isect_emit: sort_tmp required (XL tiles)");
+    MS_REQUIRE(!sort.on || !isect_ids, MS_ERR_INVALID_ARG, "isect_emit: lazy lists carry no isect_ids");
+    return emit_impl(band, bin, sort, depth_near, depth_far,
+                     EmitBuffers{means2d, radii, tile_ranges, depths, host_info, nullptr, M, sort_keys, sort_tmp, flatten_ids, isect_ids, nullptr, nullptr,
+                                 nullptr},
+                     (hipStream_t)stream_);
 }
 
-int ms::isect_emit_bins(int64_t N, const float *means2d, const int32_t *radii, const float *depths, int bin_w,
-                        int bin_h, int row_begin, int row_end, void *workspace, size_t workspace_bytes,
-                        const int32_t *bin_ranges, const int64_t *host_info, const int64_t *info_dev, int64_t cap,
-                        int flags, int lazy, float depth_near, float depth_far, uint64_t *sort_keys,
-                        const ms::BlockLists *out, const ms::DeferredTotal *defer, void *stream_) {
-    MS_REQUIRE(N > 0 && cap > 0 && cap <= 0x1fffffffll && (info_dev || host_info) && (lazy & 1), MS_ERR_INVALID_ARG,
-               "isect_emit_bins: bad N / capacity / info (block lists come from lazily sorted bins only)");
-    if (int rc = check_grid(32, bin_w, bin_h, row_begin, row_end)) return rc;
-    MS_REQUIRE(workspace && bin_ranges && means2d && radii && depths && sort_keys && out && out->block_ranges &&
+int ms::isect_emit_bins(const ms::Band &bins, const float *means2d, const int32_t *radii, const float *depths, const int32_t *bin_ranges, const int64_t *host_info,
+                        const int64_t *info_dev, int64_t cap, const ms::BinMode &bin, const ms::SortMode &sort,
+                        float depth_near, float depth_far, uint64_t *sort_keys, const ms::BlockLists *out,
+                        const ms::DeferredTotal *defer, void *stream_) {
+    MS_REQUIRE(bins.N > 0 && bins.tile_size == 32 && cap > 0 && cap <= 0x1fffffffll && (info_dev || host_info) && sort.on,
+               MS_ERR_INVALID_ARG, "isect_emit_bins: bad N / capacity / info (block lists come from lazily sorted 32-px bins only)");
+    if (int rc = check_grid(bins)) return rc;
+    MS_REQUIRE(bins.ws && bin_ranges && means2d && radii && depths && sort_keys && out && out->block_ranges &&
                    out->block_ids && out->bin_more,
                MS_ERR_INVALID_ARG, "isect_emit_bins: null pointer");
-    return emit_impl(N, means2d, radii, depths, flags, lazy | 1, depth_near, depth_far, 32, bin_w, bin_h, row_begin,
-                     row_end, workspace, workspace_bytes, bin_ranges, host_info, info_dev, cap, sort_keys, nullptr,
-                     nullptr, nullptr, (hipStream_t)stream_, out, info_dev ? defer : nullptr);
+    return emit_impl(bins, bin, sort, depth_near, depth_far,
+                     EmitBuffers{means2d, radii, bin_ranges, depths, host_info, info_dev, cap, sort_keys, nullptr, nullptr, nullptr, out,
+                                 info_dev ? defer : nullptr, nullptr},
+                     (hipStream_t)stream_);
 }
 
 extern "C" int ms_isect_offset_encode(int64_t M, const int64_t *isect_ids_sorted, int tile_w,

@@ -154,14 +154,68 @@ static inline int64_t front_redos(const int64_t *info) { return info[kInfoNeed] 
 static inline int64_t cut_redos(const int64_t *info) { return (info[kInfoNeed] >> 32) & 0x3fffffffll; }
 static inline int64_t heavy(const int64_t *info) { return info[kInfoMedium] + info[kInfoLarge] + info[kInfoXL]; }
 
+// HOW a frame is binned and sorted.  The C ABI's `tight` and `lazy` words end at the entry points: each decodes its masked
+// word once (decode_tight / decode_lazy, the only places that know a bit's value) and nothing below takes an int of flags.
+// ms_render_fwd fills the structs field by field -- the fields behind the first comment line of each are its alone.
+struct BinMode {
+    bool reach_masks, band_only, block_masks;   // bits 0-2 of `tight` (mojosplat_hip.h, ms_project_isect_count)
+    bool odd_cols, odd_rows;   // bits 3-4: the half-tile grid of a block-mask frame has 2 tile_w - 1 columns / 2 tile_h - 1 rows
+    bool band_cull;            // bit 5: the band is a rank's share of a frame -- its Gaussians are pre-culled (k_band_precull)
+    // ms_render_fwd only:
+    bool lean;          // the frame keeps LeanRecs instead of the projected arrays (the caller vouches that nobody reads those)
+    bool keep_arrays;   // ... and writes the projected arrays too (a frame that hands out last_ids)
+    bool defer_total;   // sync-free frames: the scans' total pass rides in the scatter launch
+    bool claimed;       // the count pass claims its rows (k_project_hist's tile_total); every emit of the frame must carry it too
+    int cut_in;         // a depth-cut frame: which of the two cut-off buffers it reads
+};
+struct SortMode {
+    bool on;            // `lazy` != 0: lazily sorted fronts
+    int front_level;    // bits 1-2: fronts 2^level times as deep
+    bool light_bet;     // bit 3, speculative emit: the caller expects no tile beyond the small sort class
+    // ms_render_fwd only: the merged sort launch leaves the NEXT frame's cut-offs (a depth-cut frame reads its own from the other buffer)
+    bool write_cutoffs;
+    int cut_out;        // ... in this one of the two buffers
+};
+constexpr BinMode decode_tight(int tight) {
+    return BinMode{(tight & 1) != 0, (tight & 2) != 0, (tight & 4) != 0, (tight & 8) != 0, (tight & 16) != 0, (tight & 32) != 0,
+                   false, false, false, false, 0};
+}
+constexpr SortMode decode_lazy(int lazy) { return SortMode{(lazy & 15) != 0, (lazy >> 1) & 3, (lazy & 8) != 0, false, 0}; }
+static_assert(decode_tight(1).reach_masks && decode_tight(2).band_only && decode_tight(4).block_masks && decode_tight(8).odd_cols &&
+                  decode_tight(16).odd_rows && decode_tight(32).band_cull && !decode_tight(~1).reach_masks && !decode_tight(~32).band_cull,
+              "tight: the bits mojosplat_hip.h documents, one field each");
+static_assert(!decode_lazy(0).on && decode_lazy(1).on && decode_lazy(1).front_level == 0 && decode_lazy(2).front_level == 1 &&
+                  decode_lazy(6).front_level == 3 && !decode_lazy(7).light_bet && decode_lazy(8).light_bet && decode_lazy(8).on,
+              "lazy: mojosplat_hip.h documents != 0, bits 1-2 (front level) and bit 3 (light bet)");
+static_assert(!decode_tight(~0).lean && !decode_tight(~0).keep_arrays && !decode_tight(~0).defer_total && !decode_tight(~0).claimed &&
+                  decode_tight(~0).cut_in == 0 && !decode_lazy(~0).write_cutoffs && decode_lazy(~0).cut_out == 0,
+              "no bit of a caller's word reaches what only ms_render_fwd may ask for");
+
+// WHERE: a band of tile rows of one binning grid, and the isect workspace (ms_isect_workspace_bytes(N, tw, th)) that serves it.
+// ms_render_fwd builds one per frame (one more for the 32-px bin grid of a split frame, in the same workspace).
+struct Band {
+    int64_t N;   // the scene the workspace is carved up for
+    int tile_size, tw, th, row_begin, row_end;
+    void *ws;
+    size_t ws_bytes;
+};
+// ... and how the count / scatter kernels walk the scene for it (binning.hip, make_schedule): G workgroups of `chunk` Gaussians
+struct Schedule {
+    int G;
+    int64_t chunk;
+    int64_t near_cap;   // depth-cut frames: the stride of a count workgroup's compacted records (>= what any workgroup walks, band candidates included)
+    int T_local;        // the band's tiles
+    size_t lds_bytes;   // their counters (+ the on-grid counter of the count kernels)
+};
+
 // binning.hip: ms_project_isect_count that also writes the rasteriser's records (raster_records: N x 48 B, or null;
 // they take g.colors: the frame's colours, 3 channels, f32 or f16)
-int project_isect_count(const Gaussians &g, const View &v, float radius_clip, int tile_size, int row_begin, int row_end,
-                        int tight, float *means2d, float *conics, float *depths, int32_t *radii, void *workspace,
-                        size_t workspace_bytes, int32_t *tile_ranges, int64_t *isect_info, int64_t *isect_info_mirror,
-                        void *raster_records, void *stream, uint32_t cut_stamp = 0,
+int project_isect_count(const Gaussians &g, const View &v, float radius_clip, const Band &band, BinMode mode, float *means2d,
+                        float *conics, float *depths, int32_t *radii, int32_t *tile_ranges, int64_t *isect_info,
+                        int64_t *isect_info_mirror, void *raster_records, void *stream, uint32_t cut_stamp = 0,
                         // a PREPARED scene (ms_scene_prepare): bounds of every block of block_size Gaussians, for the band pre-cull
-                        const float *block_bounds = nullptr, int block_size = 0);
+                        const float *block_bounds = nullptr, int block_size = 0,
+                        Schedule *launched = nullptr);   // out: the count launch's schedule (CutInputs::count)
 
 // Lazy sorting (binning.hip): tiles longer than front_threshold have only front_count[tile] sorted
 // entries; the rasteriser appends a tile to redo_list when pixels are still alive at the end of it.
@@ -170,10 +224,10 @@ struct CutInputs {
     Gaussians g;   // (by value: a deferred clean-up keeps the whole struct beyond the enqueuing call -- rasterize.hip, CleanupMemo)
     View v;
     void *records;
-    int tile_size;
-    // a band frame: its rows of the binning grid, and -- pre-culled (band_cull) -- the isect workspace that holds its candidate list
-    int row_begin, row_end;
-    const void *isect_workspace;
+    // the frame's band and -- pre-culled (band_cull) -- the schedule of its count launch, which left the band's candidate
+    // list in the workspace (project_isect_count: `launched`)
+    Band band;
+    Schedule count;
     int band_cull;
 };
 struct LazyLists {
@@ -249,10 +303,10 @@ int project_bwd_from_rows(const Gaussians &g, const View &v, const int32_t *radi
                           float *v_viewmat = nullptr, void *pose_scratch = nullptr);
 // project_bwd.hip: the checks of a pose-gradient entry point's output and scratch (ms_pose_scratch_bytes)
 int check_pose_out(int64_t N, const float *out, const void *scratch, size_t scratch_bytes, const char *who);
-void isect_lazy_arrays(void *workspace, int64_t N, int tile_w, int tile_h, LazyLists *out);
-bool depth_cut_fits(int64_t N, int tile_w, int tile_h);
-FrontParams front_params(int tile_size, int lazy, float depth_near, float depth_far, bool merged, bool split);
-const int32_t *isect_order_array(const void *workspace, int64_t N, int tile_w, int tile_h);
+LazyLists isect_lazy_arrays(const Band &band);
+bool depth_cut_fits(const Band &band);
+FrontParams front_params(int tile_size, const SortMode &sort, float depth_near, float depth_far, bool merged, bool split);
+const int32_t *isect_order_array(const Band &band);
 
 // rasterize.hip: ms_rasterize_to_pixels_3dgs_fwd with a separate density hint (ms_render_fwd's
 // sync-free frames pass the buffer capacity as M and the previous frame's M as the hint).
@@ -327,31 +381,25 @@ struct DeferredTotal {
     void *sync_event;
     uint32_t cut_stamp;   // != 0: a depth-cut frame; the value its tiles with dropped pairs are marked with (unique per frame)
 };
-// bits of the `tight` flags that only ms_render_fwd sets (the C entry points mask them off)
-constexpr int kTightLean = 64, kTightDeferTotal = 128, kTightDepthCutBuf = 512, kTightKeepArrays = 1024;   // (bit 10: a lean frame writes the projected arrays too)
-constexpr int kTightClaimed = 2048;   // (bit 11, round 6: the count pass claims its rows -- binning.hip, k_project_hist's tile_total; every emit of the frame must carry it too)
-//   // (bit 9: a depth-cut frame reads its cut-offs from buffer 1)
 // DEPTH CUT (sync-free lean frames on plain bins; binning.hip, k_project_hist): pairs behind their tile's cut-off
 // are counted but never written; a tile that outlives its list gets them back from the clean-up launch.
 // (project_isect_count: cut_stamp; the emit and the rasteriser: DeferredTotal::cut_stamp / LazyLists::cut_stamp)
-// binning.hip: ms_isect_tiles_emit_speculative / ms_isect_tiles_emit with the internal flag bits honoured
-int isect_emit_speculative(int64_t N, const float *means2d, const int32_t *radii, const float *depths, int tile_size,
-                           int tile_w, int tile_h, int row_begin, int row_end, void *workspace, size_t workspace_bytes,
-                           const int32_t *tile_ranges, const int64_t *isect_info_dev, int64_t capacity,
-                           const int64_t *prev_info_host, int tight, int lazy, float depth_near, float depth_far,
-                           uint64_t *sort_keys, int32_t *flatten_ids, const DeferredTotal *defer, void *stream,
+// binning.hip: what ms_isect_tiles_emit_speculative / ms_isect_tiles_emit forward to, and ms_render_fwd with its own modes
+int isect_emit_speculative(const Band &band, const float *means2d, const int32_t *radii, const float *depths, const int32_t *tile_ranges, const int64_t *isect_info_dev,
+                           int64_t capacity, const int64_t *prev_info_host, const BinMode &bin, const SortMode &sort,
+                           float depth_near, float depth_far, uint64_t *sort_keys, int32_t *flatten_ids,
+                           const DeferredTotal *defer, void *stream,
                            // non-null: the caller's rasteriser can sort the bins itself (FusedSort: filled, taken = 1 if left to it)
                            FusedSort *fuse = nullptr);
-int isect_emit_exact(int64_t N, const float *means2d, const int32_t *radii, const float *depths, int tile_size,
-                     int tile_w, int tile_h, int row_begin, int row_end, void *workspace, size_t workspace_bytes,
-                     const int32_t *tile_ranges, const int64_t *host_info, int tight, int lazy, float depth_near,
-                     float depth_far, uint64_t *sort_keys, uint64_t *sort_tmp, int32_t *flatten_ids, void *stream);
+int isect_emit_exact(const Band &band, const float *means2d, const int32_t *radii, const float *depths, const int32_t *tile_ranges, const int64_t *host_info,
+                     const BinMode &bin, const SortMode &sort, float depth_near, float depth_far, uint64_t *sort_keys,
+                     uint64_t *sort_tmp, int32_t *flatten_ids, void *stream,
+                     int64_t *isect_ids = nullptr);   // (the C entry point's: gsplat's 64-bit ids, fully sorted lists only)
 
 // binning.hip: scatter + sorts on the bin grid, writing block lists (info_dev != null: sync-free frame
 // against `cap` entries, host_info = the previous frame's record or null)
-int isect_emit_bins(int64_t N, const float *means2d, const int32_t *radii, const float *depths, int bin_w, int bin_h,
-                    int row_begin, int row_end, void *workspace, size_t workspace_bytes, const int32_t *bin_ranges,
-                    const int64_t *host_info, const int64_t *info_dev, int64_t cap, int flags, int lazy, float depth_near,
+int isect_emit_bins(const Band &bins, const float *means2d, const int32_t *radii, const float *depths, const int32_t *bin_ranges, const int64_t *host_info,
+                    const int64_t *info_dev, int64_t cap, const BinMode &bin, const SortMode &sort, float depth_near,
                     float depth_far, uint64_t *sort_keys, const BlockLists *out, const DeferredTotal *defer, void *stream);
 
 // Split frame: the block lists cut from 32-px bins are rasterised per 16x16 block and cleaned up per

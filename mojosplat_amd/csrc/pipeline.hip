@@ -68,6 +68,11 @@ WsLayout ws_layout(int64_t N, int tw, int th) {
     return L;
 }
 
+// the isect part of a frame's workspace as the binning layer wants it: every row of the tw x th grid
+ms::Band whole_grid(const WsLayout &L, const void *workspace, int64_t N, int tile_size, int tw, int th) {
+    return ms::Band{N, tile_size, tw, th, 0, th, const_cast<char *>((const char *)workspace) + L.off_isect, L.isect_bytes};
+}
+
 }  // namespace
 
 // an environment switch that is on unless set to a number equal to zero; every caller reads it once
@@ -225,8 +230,7 @@ extern "C" int ms_render_front_count_offset(int64_t N, int tile_w, int tile_h, s
                "render_front_count_offset: bad argument");
     const WsLayout L = ws_layout(N, tile_w, tile_h);
     char *base = reinterpret_cast<char *>((uintptr_t)1 << 20);   // (never dereferenced: only the arrays' places are asked for)
-    ms::LazyLists ll{};
-    ms::isect_lazy_arrays(base + L.off_isect, N, tile_w, tile_h, &ll);
+    const ms::LazyLists ll = ms::isect_lazy_arrays(whole_grid(L, base, N, 0, tile_w, tile_h));
     *offset = (size_t)((const char *)ll.front_count - base);
     return MS_OK;
 }
@@ -241,8 +245,7 @@ extern "C" int ms_render_redo_counts(const void *workspace, size_t workspace_byt
                MS_ERR_INVALID_ARG, "render_redo_counts: bad argument");
     const WsLayout L = ws_layout(N, tile_w, tile_h);
     MS_REQUIRE(workspace_bytes >= L.total, MS_ERR_WORKSPACE, "render_redo_counts: workspace %zu < %zu", workspace_bytes, L.total);
-    ms::LazyLists ll{};
-    ms::isect_lazy_arrays(const_cast<char *>((const char *)workspace) + L.off_isect, N, tile_w, tile_h, &ll);
+    const ms::LazyLists ll = ms::isect_lazy_arrays(whole_grid(L, workspace, N, 0, tile_w, tile_h));
     MS_HIP(hipMemcpyAsync(host_counts, ll.redo_count, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
     return MS_OK;
 }
@@ -331,9 +334,10 @@ static int render_fwd_impl(const ms_scene *prepared, int restart, const ms::Gaus
     // backward rasteriser walks the full lists by position; a frame that only keeps render_alphas (round 4: the
     // quad-wave backward, rasterize_bwdq.hip, walks whatever lists the forward walked, front to back) is lazily sorted
     // like any other
-    // (bits 1-2 of `lazy`: the front level the caller asked for, see MS_RENDER_FRONT_LEVEL)
-    const int lazy = (f.last_ids || !g.opacities || g.CDIM > 4 || (f.resume & MS_RENDER_FULL_SORT))
-                         ? 0 : (ms_lazy_enabled() ? 1 | (((f.resume >> 9) & 3) << 1) : 0);
+    const bool lazy = !(f.last_ids || !g.opacities || g.CDIM > 4 || (f.resume & MS_RENDER_FULL_SORT)) && ms_lazy_enabled();
+    ms::SortMode sort{};   // (the front level the caller asked for: see MS_RENDER_FRONT_LEVEL)
+    sort.on = lazy;
+    sort.front_level = lazy ? (f.resume >> 9) & 3 : 0;
     // split frame (binning.hip, emit_block_lists): bin on 32-px bins, rasterise the 16x16-block lists cut
     // from them (a band that starts or ends inside a bin row bins that whole row).  The frame is the same
     // either way.
@@ -358,8 +362,11 @@ static int render_fwd_impl(const ms_scene *prepared, int restart, const ms::Gaus
     void *records = use_records ? (void *)(ws + L.off_records) : nullptr;
     // the rasteriser launches its blocks heaviest list first (the count pass leaves the order of the binning
     // grid's tiles in the isect workspace); MOJOSPLAT_RASTER_ORDER=0: image order interleaved over the XCDs
-    const int32_t *order = ms_order_enabled() ? ms::isect_order_array(ws + L.off_isect, g.N, split ? bw : tw, split ? bh : th)
-                                              : nullptr;
+    // the frame's band on its own grid and -- a split frame -- on the 32-px bin grid it is binned on, in the same workspace
+    const ms::Band tiles{g.N, f.tile_size, tw, th, r0, r1, ws + L.off_isect, L.isect_bytes};
+    const ms::Band bins{g.N, 32, bw, bh, b0, b1, ws + L.off_isect, L.isect_bytes};
+    const ms::Band &band = split ? bins : tiles;
+    const int32_t *order = ms_order_enabled() ? ms::isect_order_array(band) : nullptr;
     // a band that is a rank's share of a frame (under 60 % of the rows of a scene worth the extra pass): the
     // Gaussians that cannot reach it are culled before the projection (binning.hip, k_band_precull).
     // MOJOSPLAT_BAND_CULL=0 switches that off.
@@ -369,13 +376,21 @@ static int render_fwd_impl(const ms_scene *prepared, int restart, const ms::Gaus
     // the scatter kernel from the 16-byte box + depth records the count kernel leaves instead)
     // (the projected arrays are for the OLDER backward -- last_ids frames -- and the caller's intermediates; the quad-wave
     // backward stages from the records and its backward projection takes the raw sums: nothing reads them)
-    const int lean = (use_records && ((uintptr_t)records & 15) == 0)
-                         ? ms::kTightLean | (f.last_ids ? ms::kTightKeepArrays : 0) : 0;
-    const int cull = ((use_records && !aux_frame && g.N >= 32768 && g.N < (1ll << 28) && 10 * (r1 - r0) < 6 * th && ms_band_cull_enabled()) ? 32 : 0) | lean;
-    const int bin_flags = 1 | 2 | 4 | ((tw & 1) ? 8 : 0) | ((th & 1) ? 16 : 0) | cull;
+    const bool lean = use_records && ((uintptr_t)records & 15) == 0;
+    const bool cull = use_records && !aux_frame && g.N >= 32768 && g.N < (1ll << 28) && 10 * (r1 - r0) < 6 * th && ms_band_cull_enabled();
+    // How every emit of the frame bins: what the frame's count pass starts from, too.  Reach masks where there are opacities to
+    // bound a reach by; a split frame's bins carry block masks for a 16-px grid of tw x th blocks.
+    ms::BinMode bin{};
+    bin.reach_masks = g.opacities != nullptr;
+    bin.band_only = true;   // (the count's: every later stage stays inside the band)
+    bin.block_masks = split;
+    bin.odd_cols = split && (tw & 1);
+    bin.odd_rows = split && (th & 1);
+    bin.band_cull = cull;
+    bin.lean = lean;
+    bin.keep_arrays = lean && f.last_ids;
     int32_t *bin_ranges = (int32_t *)(ws + L.off_bin_ranges), *bin_more = (int32_t *)(ws + L.off_bin_more);
-    ms::LazyLists lazy_lists{};
-    if (lazy) ms::isect_lazy_arrays(ws + L.off_isect, g.N, split ? bw : tw, split ? bh : th, &lazy_lists);
+    ms::LazyLists lazy_lists = lazy ? ms::isect_lazy_arrays(band) : ms::LazyLists{};
     if (lazy) lazy_lists.redo_grid = ms_redo_grid();
     bool speculated = false;
     if (phase == MS_RENDER_WHOLE || phase == MS_RENDER_BEGIN) {
@@ -406,9 +421,9 @@ static int render_fwd_impl(const ms_scene *prepared, int restart, const ms::Gaus
         // claimed rows (round 6, MOJOSPLAT_CLAIMED_ROWS=1; binning.hip, k_project_hist's tile_total): the frame's count pass and
         // EVERY emit of the frame -- the speculative one and an exact redo, in this call or a resumed one: kFrameClaimed
         // carries it there -- must agree on what a histogram row holds
-        const int claim_bit = deferred && ms_claimed_rows_enabled() ? ms::kTightClaimed : 0;
+        bin.claimed = deferred && ms_claimed_rows_enabled();
         // what every value of this frame's flag word starts from
-        const int64_t base_flags = ((cull & 32) ? ms::kFrameBandCulled : 0) | (claim_bit ? ms::kFrameClaimed : 0);
+        const int64_t base_flags = (cull ? ms::kFrameBandCulled : 0) | (bin.claimed ? ms::kFrameClaimed : 0);
         // the previous frame on this record (same scratch, same grid) had no tile beyond the small sort class:
         // bet that this one has none either (kFrameLightBet; checked against the size record below)
         const bool bet_light = !split && lazy && prev_pairs > 0 && ms::heavy(prev) == 0 && !(prev_flags & ms::kFrameExact);
@@ -432,7 +447,7 @@ static int render_fwd_impl(const ms_scene *prepared, int restart, const ms::Gaus
         const int64_t min_pairs = ms_depth_cut_min_pairs() * (int64_t)(r1 - r0) / (th > 0 ? th : 1);
         const bool cut = leaves_cutoffs && deferred && lean && !no_cut && prev_cutoffs &&
                          (prev_flags & ms::kFrameCutSigMask) == cut_grid && prev_cut_redos <= (tw * (r1 - r0)) / 64 + 4 &&
-                         (ms_depth_cut_mode() >= 2 || prev_pairs >= min_pairs) && ms::depth_cut_fits(g.N, tw, th);
+                         (ms_depth_cut_mode() >= 2 || prev_pairs >= min_pairs) && ms::depth_cut_fits(tiles);
         static std::atomic<uint32_t> cut_stamps{0};
         uint32_t cut_stamp = 0;
         if (cut)
@@ -443,17 +458,17 @@ static int render_fwd_impl(const ms_scene *prepared, int restart, const ms::Gaus
         // for the band's end.)
         const bool late_cleanup = defer_cleanup && mirror && phase == MS_RENDER_BEGIN && speculate && !split && lazy && !bet_light;
         const ms::DeferredTotal defer{1, info, (int64_t *)mirror, late_cleanup ? nullptr : f.sync_event, cut_stamp};
-        const int defer_bit = (deferred ? ms::kTightDeferTotal : 0) | (cut && cut_in ? ms::kTightDepthCutBuf : 0) | claim_bit;
-        const ms::CutInputs cut_inputs{g, v, records, f.tile_size, r0, r1, ws + L.off_isect, (cull & 32) ? 1 : 0};
+        ms::BinMode count_mode = bin;
+        count_mode.defer_total = deferred;
+        count_mode.cut_in = cut ? cut_in : 0;
+        ms::CutInputs cut_inputs{g, v, records, tiles, ms::Schedule{}, cull ? 1 : 0};   // (.count: from the count pass below)
         const int64_t cut_bits = (cut ? ms::kFrameDepthCut : 0) |
                                  (leaves_cutoffs ? (ms::kFrameCutoffs | ((int64_t)cut_out << ms::kFrameCutoffsBufShift) | cut_grid) : 0);
-        if (int rc = ms::project_isect_count(g, v, /*radius_clip=*/0.0f, split ? 32 : f.tile_size, split ? b0 : r0, split ? b1 : r1,
-                                             /*tight | ranges for the band only (| block masks)=*/(split ? bin_flags : 1 | 2 | cull) | defer_bit,
-                                             means2d, conics, depths, radii, ws + L.off_isect, L.isect_bytes,
+        if (int rc = ms::project_isect_count(g, v, /*radius_clip=*/0.0f, band, count_mode, means2d, conics, depths, radii,
                                              split ? bin_ranges : ranges, info, (int64_t *)mirror, records, stream, cut_stamp,
                                              // (a prepared scene: the band pre-cull skips the blocks that cannot reach the band)
-                                             prepared && prepared->block_bounds && (cull & 32) ? prepared->block_bounds : nullptr,
-                                             prepared ? prepared->block_size : 0))
+                                             prepared && prepared->block_bounds && cull ? prepared->block_bounds : nullptr,
+                                             prepared ? prepared->block_size : 0, split ? nullptr : &cut_inputs.count))
             return rc;
         mark(1);
         MS_HP_T(hp_t3);
@@ -475,9 +490,8 @@ static int render_fwd_impl(const ms_scene *prepared, int restart, const ms::Gaus
             int32_t *ids = (int32_t *)((char *)f.isect_buf + ms::align_up((size_t)c * 8, 256));
             if (split) {
                 const ms::BlockLists lists{ranges, (int32_t *)((char *)ids + ms::align_up((size_t)c * 4, 256)), bin_more, tw, th};
-                if (int rc = ms::isect_emit_bins(g.N, means2d, radii, depths, bw, bh, b0, b1, ws + L.off_isect,
-                                                 L.isect_bytes, bin_ranges, prev, info, c, bin_flags | claim_bit, lazy,
-                                                 v.near_plane, v.far_plane, keys, &lists, deferred ? &defer : nullptr, stream))
+                if (int rc = ms::isect_emit_bins(bins, means2d, radii, depths, bin_ranges, prev, info, c, bin, sort, v.near_plane, v.far_plane,
+                                                 keys, &lists, deferred ? &defer : nullptr, stream))
                     return rc;
                 mark(2);
                 lazy_lists.keys = keys;
@@ -497,16 +511,16 @@ static int render_fwd_impl(const ms_scene *prepared, int restart, const ms::Gaus
             // levels and full-sort lanes keep the two launches.
             ms::FusedSort fuse{};
             const int fuse_mode = ms_fused_sort_mode();
-            const bool ask_fuse = (fuse_mode & 3) != 0 && lazy == 1 && !bet_light && !aux_frame && !list_nq && !zero_rows && clip0 < 0 &&
+            const bool ask_fuse = (fuse_mode & 3) != 0 && lazy && sort.front_level == 0 && !bet_light && !aux_frame && !list_nq && !zero_rows && clip0 < 0 &&
                                   ms_merged_sort_enabled() &&
                                   ms::rasterize_takes_sort(prev_pairs > 0 ? prev_pairs : c, g.CDIM, v.W, v.H, f.tile_size, r0, r1, records,
                                                            order, (fuse_mode & 3) >= 2);
-            if (int rc = ms::isect_emit_speculative(g.N, means2d, radii, depths, f.tile_size, tw, th, r0, r1,
-                                                    ws + L.off_isect, L.isect_bytes, ranges, info, c, prev,
-                                                    /*tight=*/(g.opacities != nullptr ? 1 : 0) | cull | claim_bit,
-                                                    lazy | (bet_light ? 8 : 0) | (leaves_cutoffs ? 32 | (cut_out << 4) : 0),
-                                                    v.near_plane, v.far_plane, keys, ids, deferred ? &defer : nullptr, stream,
-                                                    ask_fuse ? &fuse : nullptr))
+            ms::SortMode spec_sort = sort;
+            spec_sort.light_bet = bet_light;
+            spec_sort.write_cutoffs = leaves_cutoffs;
+            spec_sort.cut_out = leaves_cutoffs ? cut_out : 0;
+            if (int rc = ms::isect_emit_speculative(tiles, means2d, radii, depths, ranges, info, c, prev, bin, spec_sort, v.near_plane, v.far_plane,
+                                                    keys, ids, deferred ? &defer : nullptr, stream, ask_fuse ? &fuse : nullptr))
                 return rc;
             mark(2);
             MS_HP_T(hp_t5);
@@ -609,6 +623,7 @@ static int render_fwd_impl(const ms_scene *prepared, int restart, const ms::Gaus
     MS_REQUIRE(f.isect_buf && f.isect_bytes >= need, MS_ERR_WORKSPACE,
                "render_fwd: intersection buffer %zu < %zu (grow it and call again with resume=1)", f.isect_bytes,
                need);
+    bin.claimed = (flags & ms::kFrameClaimed) != 0;   // (as the frame's count pass left its rows, in this call or an earlier one)
     char *ib = (char *)f.isect_buf;
     const size_t key_bytes = ms::align_up((size_t)M * 8, 256);
     uint64_t *keys = (uint64_t *)ib;
@@ -618,9 +633,8 @@ static int render_fwd_impl(const ms_scene *prepared, int restart, const ms::Gaus
     if (split) {
         const int64_t c = M > 0 ? M : 1;
         const ms::BlockLists lists{ranges, (int32_t *)((char *)ids + ms::align_up((size_t)M * 4, 256)), bin_more, tw, th};
-        if (int rc = ms::isect_emit_bins(g.N, means2d, radii, depths, bw, bh, b0, b1, ws + L.off_isect, L.isect_bytes,
-                                         bin_ranges, host, nullptr, c, bin_flags | ((flags & ms::kFrameClaimed) ? ms::kTightClaimed : 0), lazy, v.near_plane, v.far_plane,
-                                         keys, &lists, nullptr, stream))
+        if (int rc = ms::isect_emit_bins(bins, means2d, radii, depths, bin_ranges, host, nullptr, c, bin, sort, v.near_plane, v.far_plane, keys, &lists,
+                                         nullptr, stream))
             return rc;
         if (!speculated) mark(2);
         lazy_lists.keys = keys;
@@ -629,9 +643,7 @@ static int render_fwd_impl(const ms_scene *prepared, int restart, const ms::Gaus
                                        records, order,
                                        (!speculated && f.stage_events) ? f.stage_events[3] : nullptr, stream);
     }
-    if (int rc = ms::isect_emit_exact(g.N, means2d, radii, depths, f.tile_size, tw, th, r0, r1, ws + L.off_isect,
-                                      L.isect_bytes, ranges, host, /*tight=*/(g.opacities != nullptr ? 1 : 0) | cull | ((flags & ms::kFrameClaimed) ? ms::kTightClaimed : 0), lazy, v.near_plane, v.far_plane,
-                                      keys, tmp, ids, stream))
+    if (int rc = ms::isect_emit_exact(tiles, means2d, radii, depths, ranges, host, bin, sort, v.near_plane, v.far_plane, keys, tmp, ids, stream))
         return rc;
     if (!speculated) mark(2);
     lazy_lists.keys = keys;
@@ -727,10 +739,10 @@ static int render_bwd_rows_impl(int64_t N, int CDIM, int W, int H, int tile_size
         MS_HIP(hipMemsetAsync(rows, 0, (size_t)N * 16 * sizeof(float), stream));
     // a lazily sorted frame: the lists are sorted as deep as the forward rasteriser walked them -- the tiles whose
     // front ran out were redone by the forward's clean-up pass and are this call's second launch (normally empty)
-    ms::LazyLists ll{};
-    ms::isect_lazy_arrays(const_cast<char *>(ws) + L.off_isect, N, tw, th, &ll);
+    const ms::Band grid = whole_grid(L, ws, N, tile_size, tw, th);
+    const ms::LazyLists ll = ms::isect_lazy_arrays(grid);
     const bool fronts = (flags & ms::kFrameFronts) != 0;
-    const int32_t *order = ms_order_enabled() ? ms::isect_order_array(ws + L.off_isect, N, tw, th) : nullptr;
+    const int32_t *order = ms_order_enabled() ? ms::isect_order_array(grid) : nullptr;
     if (int rc = ms::rasterize_bwd_quads(N, M, records, backgrounds, W, H, tile_size, ranges, ids, 1,
                                          fronts ? ll.front_count : nullptr, ll.front_threshold, fronts ? ll.redo_flag : nullptr,
                                          render_colors, render_alphas, v_render_colors, v_render_alphas, rows, order, stream_, r0, r1,
@@ -873,7 +885,7 @@ static int render_bwd_impl(const ms::Gaussians &g, const ms::View &v, int tile_s
                                    render_alphas, last_ids, v_render_colors, v_render_alphas, v_means2d, v_conics, v_colors,
                                    v_opacities, rb ? bw : nullptr, rb, /*overwrite: 2 = leave the rows packed=*/packed_rows ? 2 : 1, records,
                                    // (a whole-image frame on 16-px tiles: its count pass ordered exactly these blocks)
-                                   (tile_size == 16 && ms_order_enabled()) ? ms::isect_order_array(ws + L.off_isect, g.N, tw, th) : nullptr,
+                                   (tile_size == 16 && ms_order_enabled()) ? ms::isect_order_array(whole_grid(L, ws, g.N, tile_size, tw, th)) : nullptr,
                                    stream_))
         return rc;
     if (mid_event) MS_HIP(hipEventRecord((hipEvent_t)mid_event, stream));   // (in-situ timing: between the two stages)

@@ -138,6 +138,17 @@ def test_c_abi_exports_every_declared_symbol():
     assert Lt.ms_isect_workspace_bytes(1000, 120, 68) > 0
 
 
+@pytest.mark.parametrize("N,tile_w,tile_h,expected", [
+    (0, 1, 1, 8_423_936), (1, 1, 1, 8_423_936), (1_000, 3, 2, 8_477_696), (100_000, 40, 23, 14_784_768),
+    (1_000_000, 60, 34, 56_775_680), (1_000_000, 120, 68, 69_848_832), (3_000_000, 240, 135, 209_626_112),
+    (2 ** 28, 255, 255, 11_958_474_240), (5, 0, 4, 0), (5, 40_000, 40_000, 0)])
+def test_isect_workspace_bytes_is_abi(N, tile_w, tile_h, expected):
+    """ms_isect_workspace_bytes is ABI: callers size and cache scratch by it, and the arrays that do not depend on N keep
+    their places when a scene grows.  The figures are what the library returned before the workspace's carve-up became a
+    typed view (binning.hip, Layout); a change of order, size or alignment of any array moves at least one of them."""
+    assert _hip.load().ms_isect_workspace_bytes(N, tile_w, tile_h) == expected
+
+
 def test_c_abi_argument_validation_returns_status_codes():
     """Every entry point validates its arguments BEFORE touching the device and reports through the
     status code + ms_last_error_string (no exception crosses the ABI) -- checkable
