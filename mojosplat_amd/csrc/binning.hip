@@ -1064,6 +1064,8 @@ struct ScanTotalArgs {
     // segment from eight counter arrays, one per XCD (xtot[x * T_local + t]): a tile's count is their sum (the total pass
     // writes it to tile_count), and the stretch of XCD x starts behind those of the XCDs before it
     const uint32_t *xtot;
+    // a frame whose rasteriser sorts its bins itself (deferred total pass only): one record per position of `order`
+    ms::OrderRec *order_recs;
 };
 
 // a tile's count in the deferred passes: the prefix kernel's, or the sum of the eight XCDs' claims
@@ -1428,9 +1430,18 @@ __device__ __forceinline__ void deferred_total(int which, const ScanTotalArgs &A
         }
         __syncthreads();
         if (tid == 0 && A.wg_on_grid) const_cast<uint32_t *>(A.wg_on_grid)[kMaxG + 1] = s_base[kLightBucket];   // (see tile_scan_total)
+        // (a fused frame: the bins' starts, the prefix the other workgroups take -- s[t], s[t + 1] are what which == 0 writes to
+        // tile_ranges, saturation included -- so that a position's record names its bin AND its list)
+        if (A.order_recs) {
+            const unsigned long long grand = tile_prefix_lds(A.tile_count, T_local, s, nullptr, A.xtot);
+            if (tid == 0) s[T_local] = (uint32_t)min(grand, 0x7fffffffull);
+        }
         __syncthreads();
-        for (int t = tid; t < T_local; t += kHistThreads)
-            A.order[atomicAdd(&s_base[bucket_of(tile_count_of(A, t, T_local))], 1u)] = band0 + t;
+        for (int t = tid; t < T_local; t += kHistThreads) {
+            const unsigned int p = atomicAdd(&s_base[bucket_of(tile_count_of(A, t, T_local))], 1u);
+            A.order[p] = band0 + t;
+            if (A.order_recs) A.order_recs[p] = ms::OrderRec{band0 + t, (int32_t)s[t], (int32_t)(s[t + 1] - s[t]), 0};
+        }
         return;
     }
     if (A.far_zero)   // (depth-cut frame: the clean-up launches' per-tile counts and cursors; every tile of the grid)
@@ -2760,6 +2771,7 @@ int emit_impl(const Band &band, const ms::BinMode &bin, const ms::SortMode &sort
         // (claimed rows: the count pass of this frame claimed its rows per XCD -- the cursors of either scatter form add the
         // stretches of the XCDs before the workgroup's own)
         A.xtot = bin.claimed && p.T_local > 0 ? ws.claims : nullptr;
+        if (deferred && fuse) A.order_recs = fuse->order_recs;
         if (deferred && defer->cut_stamp) {
             MS_REQUIRE(lean12 && lazy, MS_ERR_INVALID_ARG, "isect emit: a depth-cut frame must be a lean, lazily sorted frame on plain bins");
             A.wg_far = ws.wg_far;
@@ -2830,8 +2842,9 @@ int emit_impl(const Band &band, const ms::BinMode &bin, const ms::SortMode &sort
             const ms::FrontParams fp = ms::front_params(tile_size, sort, depth_near, depth_far, merged, bl.block_ids != nullptr);
             // The rasteriser sorts each bin in the workgroup that rasterises it (rasterize.hip, k_sort_rasterize): the merged
             // launch on 32-px bins at the default front depth (2048 keys of LDS room) is left to it, with what it would have taken
-            if (fuse && merged && spec && tile_size == 32 && fp.front_cap <= 2048) {
-                *fuse = ms::FusedSort{1, fp, ws.depth_wg, p.G, ws.order, p.T_local, tau_next, tau_now, ws.has_far,
+            // (... a frame whose total pass rode in the scatter launch above: that pass wrote the per-position records)
+            if (fuse && fuse->order_recs && defer && merged && spec && tile_size == 32 && fp.front_cap <= 2048) {
+                *fuse = ms::FusedSort{1, fp, ws.depth_wg, p.G, fuse->order_recs, p.T_local, tau_next, tau_now, ws.has_far,
                                       cut_stamp, cap, sort_keys, flatten_ids, ws.front_count};
                 return MS_OK;
             }

@@ -272,13 +272,20 @@ struct FrontParams {
 // (binning.hip, k_tile_front<false, true>) would have been handed.  isect_emit_speculative fills it and launches the scatter
 // alone (taken = 1) when it would have launched the merged sort on 32-px bins at the default front depth; rasterize_fwd
 // then launches the fused kernel in place of its own.
+// What the workgroup at position p of the heaviest-first order needs to begin: its bin and the bin's list, in ONE load.  The
+// pass that builds the order writes it (binning.hip, deferred_total) beside order[] and tile_ranges[], which stay as they are.
+struct alignas(16) OrderRec {
+    int32_t tile, start, n, pad;
+};
 struct FusedSort {
     int taken;              // out: the sort launch was left to the rasteriser
     FrontParams fp;
-    const uint32_t *wg_depth;   // the scatter's per-workgroup depth ranges, n_wg pairs
+    const uint32_t *wg_depth;   // the scatter's per-workgroup depth ranges, n_wg pairs (8-byte aligned)
     int n_wg;
-    const int32_t *order;   // the band's bins, heaviest first, n_order of them: one workgroup each
-    int n_order;
+    // in: n_order OrderRecs of the caller's own scratch (null: the frame is not fused); the scatter launch of a fused frame
+    // fills all of them, every frame
+    OrderRec *order_recs;
+    int n_order;            // the band's bins, heaviest first: one workgroup each
     uint32_t *tau_out;      // the next frame's cut-offs (or null), this frame's, the marks of its cut bins and their stamp
     const uint32_t *tau_now, *has_far;
     uint32_t cut_stamp;

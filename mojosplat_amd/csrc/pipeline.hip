@@ -42,7 +42,7 @@ namespace {
 
 struct WsLayout {
     size_t off_isect, isect_bytes, off_means2d, off_conics, off_depths, off_radii, off_ranges, off_info, off_bin_ranges,
-        off_bin_more, off_records, off_quad_counts, off_rows, total;
+        off_bin_more, off_records, off_quad_counts, off_order_recs, off_rows, total;
 };
 
 WsLayout ws_layout(int64_t N, int tw, int th) {
@@ -60,6 +60,7 @@ WsLayout ws_layout(int64_t N, int tw, int th) {
     L.off_bin_more = o;   o += ms::align_up(T * 4, 256);
     L.off_records = o;    o += ms::align_up(n * sizeof(ms::RasterRecord), 256);   // the rasteriser's ready-made records
     L.off_quad_counts = o; o += ms::align_up(T * 64 * 4, 256);   // a differentiable frame: entries of every 8x8 quad's list (<= 64 quads a tile: bins of 64 px)
+    L.off_order_recs = o; o += ms::align_up(T * sizeof(ms::OrderRec), 256);   // a fused frame: bin and list per position of the heaviest-first order
     // round 6: a differentiable frame's rows of raw gradient sums (ms_render_bwd_rows: f32[N][16]) -- the LAST region, so that a
     // caller finds it at ms_render_workspace_bytes() - ms_render_bwd_rows_bytes(N): the frame's rasteriser zeroes it on its way
     // (bit 15 of the record's flag word says so) and ms_render_bwd_rows, handed exactly this address, skips its memset
@@ -510,6 +511,7 @@ static int render_fwd_impl(const ms_scene *prepared, int restart, const ms::Gaus
             // cut-off rules, the rasteriser's own are untouched); bands, differentiable frames, light-bet frames, deeper front
             // levels and full-sort lanes keep the two launches.
             ms::FusedSort fuse{};
+            fuse.order_recs = (ms::OrderRec *)(ws + L.off_order_recs);
             const int fuse_mode = ms_fused_sort_mode();
             const bool ask_fuse = (fuse_mode & 3) != 0 && lazy && sort.front_level == 0 && !bet_light && !aux_frame && !list_nq && !zero_rows && clip0 < 0 &&
                                   ms_merged_sort_enabled() &&

@@ -792,13 +792,24 @@ __global__ __launch_bounds__(kFusedThreads, 6) void k_sort_rasterize(RasterArgs 
     __shared__ int32_t s_ids[kFusedCap];
     if ((int)blockIdx.x >= S.n_order) return;
     MS_DIAG_ONLY(const unsigned long long diag_wg0 = __builtin_amdgcn_s_memrealtime();)
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x, w = tid >> 6;
+    MS_DIAG_ONLY(const int lane = tid & 63;)
     // (the sort phase at raised priority: its few instructions between barriers go ahead of the resident rasterising waves,
     // and the workgroup reaches its own VALU-bound phase sooner -- 158.8 / 158.9 us a frame against 159.3 / 160.3 at config 3)
     __builtin_amdgcn_s_setprio(3);
-    const int tile = S.order[blockIdx.x];
+    // ONE load tells the workgroup its bin and the bin's list (ms::OrderRec, written with the order itself), and the frame's
+    // per-workgroup depth ranges -- which no bin decides -- are asked for in the same breath: a heavy bin consumes them behind
+    // its keys' trip (front_select_lds), so that two trips to memory, not five, come before the first record is gathered.
+    const ms::OrderRec rec = S.order_recs[blockIdx.x];
+    uint32_t part_lo = 0xffffffffu, part_hi = 0u;   // (n_wg <= kFusedThreads: rasterize_fwd)
+    if (S.wg_depth && tid < S.n_wg) {
+        const uint2 r = reinterpret_cast<const uint2 *>(S.wg_depth)[tid];
+        part_lo = r.x;
+        part_hi = r.y;
+    }
+    const int tile = rec.tile;
     int len = 0;   // sorted ids in s_ids (uniform)
-    const int start = A.tile_ranges[2 * tile], n = A.tile_ranges[2 * tile + 1] - start;
+    const int start = rec.start, n = rec.n;
     // (a bin that walks on behind its front) the smallest key not yet consumed, as two scalars
     bool walks_on = false;
     uint32_t wlo_lo = 0u, wlo_hi = 0u;
@@ -826,34 +837,9 @@ __global__ __launch_bounds__(kFusedThreads, 6) void k_sort_rasterize(RasterArgs 
             uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_out + kFusedCap);
             uint32_t *s_red = s_cnt + kFrontNB;
             int *s_sel = reinterpret_cast<int *>(s_red + 64);
-            // the frame's own depth range (per-workgroup min / max left by the scatter) beats the camera planes
-            uint32_t fixed_min = S.fp.fixed_min;
-            int fixed_shift = S.fp.fixed_shift;
-            if (S.wg_depth) {
-                uint32_t lo = 0xffffffffu, hi = 0u;
-                for (int j = tid; j < S.n_wg; j += kFusedThreads) {
-                    lo = min(lo, S.wg_depth[2 * j]);
-                    hi = max(hi, S.wg_depth[2 * j + 1]);
-                }
-#pragma unroll
-                for (int d = 32; d > 0; d >>= 1) {
-                    lo = min(lo, (uint32_t)__shfl_xor((int)lo, d));
-                    hi = max(hi, (uint32_t)__shfl_xor((int)hi, d));
-                }
-                if (lane == 0) { s_red[w] = lo; s_red[16 + w] = hi; }
-                __syncthreads();
-#pragma unroll
-                for (int ww = 0; ww < NW; ++ww) { lo = min(lo, s_red[ww]); hi = max(hi, s_red[16 + ww]); }
-                __syncthreads();
-                if (hi >= lo) {
-                    const uint32_t span = hi - lo;
-                    const int bits = span ? 32 - __clz(span) : 0;
-                    fixed_min = lo;
-                    fixed_shift = max(0, bits - kFrontLogNB);
-                }
-            }
-            len = front_select_lds<kFusedThreads, 4>(S.keys + start, n, s_out, s_cnt, s_red, s_sel, fixed_min, fixed_shift,
-                                                     S.fp.front_k, min(S.fp.front_cap, kFusedCap));
+            // (the frame's own depth range -- per-workgroup min / max left by the scatter, reduced inside -- beats the camera planes)
+            len = front_select_lds<kFusedThreads, 4>(S.keys + start, n, s_out, s_cnt, s_red, s_sel, S.fp.fixed_min, S.fp.fixed_shift,
+                                                     S.fp.front_k, min(S.fp.front_cap, kFusedCap), S.wg_depth != nullptr, part_lo, part_hi);
             if (tid == 0) {
                 S.front_count[tile] = len;
                 if (S.tau_out) {
@@ -1653,7 +1639,8 @@ int ms::rasterize_fwd(int64_t N, int64_t M, int64_t density_hint, const float *m
     if (fused) {
         // the frame's sort was left to this launch: the caller asked rasterize_takes_sort first, and the rest is what it could not see
         MS_REQUIRE(A.records && lazy && lazy->front_count && lazy->front_threshold == kFrontK && order && !last_ids && !A.quad_lists &&
-                       !zero_mem && clip_row16_begin < 0 && tile_size == 32 && fused->n_order == band_tiles && fused->fp.front_cap <= kFusedCap && M == fused->cap,
+                       !zero_mem && clip_row16_begin < 0 && tile_size == 32 && fused->n_order == band_tiles && fused->fp.front_cap <= kFusedCap && M == fused->cap &&
+                       fused->order_recs && fused->n_wg <= kFusedThreads,
                    MS_ERR_INVALID_ARG, "rasterize_fwd: this frame cannot sort its bins in the rasteriser");
         A.parts = 2;
     }

@@ -1,6 +1,7 @@
 // Per-tile sorting in LDS for the binning kernels (binning.hip): the counting sort of a whole list and the
 // selection + sort of a heavy list's front.  Device code only.
 #pragma once
+#include <type_traits>
 #include "ms_common.hpp"
 
 namespace {
@@ -15,6 +16,32 @@ namespace {
 // smaller than itself (full 64-bit compare) and moves to that rank.  ~6 barriers per tile instead of the O(log^2 n) of a
 // bitonic network.  If some bucket is crowded (many identical depths) the tile falls back to
 // the bitonic network below, which is oblivious to the key distribution.
+// Wave-wide inclusive scan on the DPP path: shifts inside the rows of 16 lanes, then the two row broadcasts.  A step is a
+// VALU instruction; __shfl_up / __shfl_xor go through the LDS crossbar (ds_bpermute), a round trip a step, and the sorts
+// below ran twelve to twenty-four of those in a row between their barriers.  Every lane of the wave must be active.
+// ident: op's neutral element (what a lane without a source reads).  Lane 63 holds the reduction (wave_reduce).
+template <typename Op>
+__device__ __forceinline__ uint32_t wave_scan(uint32_t x, uint32_t ident, Op op) {
+    auto from = [&](auto ctrl, auto rows) __attribute__((always_inline)) {
+        return (uint32_t)__builtin_amdgcn_update_dpp((int)ident, (int)x, decltype(ctrl)::value, decltype(rows)::value, 0xf, false);
+    };
+    using std::integral_constant;
+    x = op(x, from(integral_constant<int, 0x111>{}, integral_constant<int, 0xf>{}));   // row_shr:1
+    x = op(x, from(integral_constant<int, 0x112>{}, integral_constant<int, 0xf>{}));   // row_shr:2
+    x = op(x, from(integral_constant<int, 0x114>{}, integral_constant<int, 0xf>{}));   // row_shr:4
+    x = op(x, from(integral_constant<int, 0x118>{}, integral_constant<int, 0xf>{}));   // row_shr:8
+    x = op(x, from(integral_constant<int, 0x142>{}, integral_constant<int, 0xa>{}));   // row_bcast:15 into rows 1 and 3
+    x = op(x, from(integral_constant<int, 0x143>{}, integral_constant<int, 0xc>{}));   // row_bcast:31 into rows 2 and 3
+    return x;
+}
+template <typename Op>
+__device__ __forceinline__ uint32_t wave_reduce(uint32_t x, uint32_t ident, Op op) {
+    return (uint32_t)__builtin_amdgcn_readlane((int)wave_scan(x, ident, op), 63);
+}
+__device__ __forceinline__ uint32_t wave_min(uint32_t x) { return wave_reduce(x, 0xffffffffu, [](uint32_t a, uint32_t b) { return min(a, b); }); }
+__device__ __forceinline__ uint32_t wave_max(uint32_t x) { return wave_reduce(x, 0u, [](uint32_t a, uint32_t b) { return max(a, b); }); }
+__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t x) { return wave_scan(x, 0u, [](uint32_t a, uint32_t b) { return a + b; }); }
+
 template <int THREADS>
 __device__ __forceinline__ void bitonic_sort_lds(uint64_t *s, int P) {
     for (int k = 2; k <= P; k <<= 1) {
@@ -145,11 +172,8 @@ __device__ __forceinline__ void sort_segment_lds(unsigned char *smem, const uint
             kmax = max(kmax, hi);
         }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        kmin = min(kmin, (uint32_t)__shfl_xor((int)kmin, d));
-        kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, d));
-    }
+    kmin = wave_min(kmin);
+    kmax = wave_max(kmax);
     if (lane == 0) { s_red[w] = kmin; s_red[16 + w] = kmax; }
     const int B = min(Cfg::NB, max(64, 2 * next_pow2(n)));
     for (int b = tid; b < B; b += THREADS) s_cnt[b] = 0;
@@ -177,24 +201,18 @@ __device__ __forceinline__ void sort_segment_lds(unsigned char *smem, const uint
         sum += local[q];
         cmax = max(cmax, local[q]);
     }
-    uint32_t incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)incl, d);
-        if (lane >= d) incl += o;
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) cmax = max(cmax, (uint32_t)__shfl_xor((int)cmax, d));
-    sync();  // s_red reuse
-    if (lane == 63) s_red[w] = incl;
-    if (lane == 0) s_red[16 + w] = cmax;
+    const uint32_t incl = wave_incl_sum(sum);
+    cmax = wave_max(cmax);
+    // (words 32.. of the reduction scratch: the range's words 0..31 may still be being read, and no barrier is spent on that)
+    if (lane == 63) s_red[32 + w] = incl;
+    if (lane == 0) s_red[48 + w] = cmax;
     sync();
     uint32_t run = incl - sum;
     cmax = 0;
 #pragma unroll
     for (int ww = 0; ww < NW; ++ww) {
-        if (ww < w) run += s_red[ww];
-        cmax = max(cmax, s_red[16 + ww]);
+        if (ww < w) run += s_red[32 + ww];
+        cmax = max(cmax, s_red[48 + ww]);
     }
 #pragma unroll
     for (int q = 0; q < (int)(sizeof(local) / 4); ++q) {
@@ -255,6 +273,8 @@ __device__ __forceinline__ void sort_segment_lds(unsigned char *smem, const uint
 
 
 // ---- lazily sorted fronts: selection + sort of the nearest keys of a heavy list (k_tile_front) --------
+// (the list's first kLoads * THREADS keys are loaded ONCE and serve all three passes from registers; the passes read only the
+// remainder of a longer list from memory)
 // pass A: min / max of the depth bits (skipped when the caller knows a range);  pass B: LDS histogram over kFrontNB
 // order-preserving buckets;  scan;  b* = first bucket whose inclusive prefix reaches front_k;  pass C: keys of buckets
 // <= b* go to LDS, rank themselves inside their bucket (as in sort_segment_lds) and drop into place.
@@ -271,37 +291,68 @@ static_assert((1 << kFrontLogNB) == kFrontNB, "bucket count");
 template <int THREADS, int kLoads>
 __device__ __forceinline__ int front_select_lds(const uint64_t *__restrict__ kin, int n, uint64_t *s_out, uint32_t *s_cnt,
                                                 uint32_t *s_red, int *s_sel, uint32_t fixed_min, int fixed_shift, int front_k,
-                                                int front_cap) {
+                                                int front_cap,
+                                                // (uniform) part_lo / part_hi: this thread's share of the frame's per-workgroup
+                                                // depth ranges, still to be reduced -- here, behind the barrier that publishes the
+                                                // zeroed counters; an empty range (hi < lo) leaves fixed_min / fixed_shift standing
+                                                bool frame_part = false, uint32_t part_lo = 0xffffffffu, uint32_t part_hi = 0u) {
     constexpr int NW = THREADS / 64;
     constexpr int kRank = kFrontCap / THREADS;   // keys a thread ranks
+    constexpr int kRegs = kLoads * THREADS;      // the list's first keys stay in registers from here to the selection
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    // A. depth-bit range: the camera's [near, far] when the caller knows it (every surviving
+    // The keys of the first kRegs positions: ONE trip to memory, on its way before anything below waits, serves the range
+    // pass (if there is one), the histogram and the selection.  Only the remainder of a longer list is read once per pass.
+    uint64_t kreg[kLoads];
+#pragma unroll
+    for (int u = 0; u < kLoads; ++u) kreg[u] = kin[min(u * THREADS + tid, n - 1)];   // (unconditional: the loads issue together)
+    // A. depth-bit range: the frame's own or the camera's [near, far] when the caller knows one (every surviving
     //    depth lies inside, so the pass over the keys is saved), else the tile's own min / max
+    // (reduction words: [0, 32) the frame's range, [32, 64) the tile's own -- and, behind the histogram's barrier, the scan's
+    // wave totals: no barrier exists only to hand a word from one stage to the next)
     uint32_t kmin = fixed_min;
     int shift = fixed_shift;
     for (int b = tid; b < kFrontNB; b += THREADS) s_cnt[b] = 0;
-    if (fixed_shift < 0) {
+    if (tid == 0) { s_sel[0] = -1; s_sel[1] = 0; s_sel[3] = 0; }
+    if (frame_part) {
+        part_lo = wave_min(part_lo);
+        part_hi = wave_max(part_hi);
+        if (lane == 0) { s_red[w] = part_lo; s_red[16 + w] = part_hi; }
+    }
+    if (frame_part || fixed_shift >= 0) __syncthreads();
+    if (frame_part) {
+#pragma unroll
+        for (int ww = 0; ww < NW; ++ww) { part_lo = min(part_lo, s_red[ww]); part_hi = max(part_hi, s_red[16 + ww]); }
+        if (part_hi >= part_lo) {
+            const uint32_t span = part_hi - part_lo;
+            const int bits = span ? 32 - __clz(span) : 0;
+            kmin = part_lo;
+            shift = max(0, bits - kFrontLogNB);
+        }
+    }
+    if (shift < 0) {
         uint32_t kmax = 0u;
         kmin = 0xffffffffu;
-        for (int i = tid; i < n; i += THREADS) {
+#pragma unroll
+        for (int u = 0; u < kLoads; ++u)
+            if (u * THREADS + tid < n) {
+                const uint32_t d = (uint32_t)(kreg[u] >> 32);
+                kmin = min(kmin, d);
+                kmax = max(kmax, d);
+            }
+        for (int i = kRegs + tid; i < n; i += THREADS) {
             const uint32_t d = (uint32_t)(kin[i] >> 32);
             kmin = min(kmin, d);
             kmax = max(kmax, d);
         }
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            kmin = min(kmin, (uint32_t)__shfl_xor((int)kmin, d));
-            kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, d));
-        }
-        if (lane == 0) { s_red[w] = kmin; s_red[16 + w] = kmax; }
+        kmin = wave_min(kmin);
+        kmax = wave_max(kmax);
+        if (lane == 0) { s_red[32 + w] = kmin; s_red[48 + w] = kmax; }
         __syncthreads();
 #pragma unroll
-        for (int ww = 0; ww < NW; ++ww) { kmin = min(kmin, s_red[ww]); kmax = max(kmax, s_red[16 + ww]); }
+        for (int ww = 0; ww < NW; ++ww) { kmin = min(kmin, s_red[32 + ww]); kmax = max(kmax, s_red[48 + ww]); }
         const uint32_t span = kmax - kmin;
         const int bits = span ? 32 - __clz(span) : 0;
         shift = max(0, bits - kFrontLogNB);
-    } else {
-        __syncthreads();
     }
     // B. histogram
     auto bucket_of = [&](uint64_t k) -> int {
@@ -309,10 +360,13 @@ __device__ __forceinline__ int front_select_lds(const uint64_t *__restrict__ kin
         const uint32_t b = (d > kmin ? d - kmin : 0u) >> shift;
         return (int)min(b, (uint32_t)(kFrontNB - 1));
     };
-    // (both passes over the keys fetch kLoads keys per thread before touching them: one memory round trip
+#pragma unroll
+    for (int u = 0; u < kLoads; ++u)
+        if (u * THREADS + tid < n) atomicAdd(&s_cnt[bucket_of(kreg[u])], 1u);
+    // (both passes over the remainder fetch kLoads keys per thread before touching them: one memory round trip
     // per kLoads * THREADS keys instead of one per THREADS -- the kernel lasts as long as its largest
     // list takes, and that was 2 x n / THREADS dependent round trips)
-    for (int i0 = 0; i0 < n; i0 += kLoads * THREADS) {
+    for (int i0 = kRegs; i0 < n; i0 += kLoads * THREADS) {
         uint32_t d[kLoads];
 #pragma unroll
         for (int u = 0; u < kLoads; ++u) {
@@ -329,20 +383,13 @@ __device__ __forceinline__ int front_select_lds(const uint64_t *__restrict__ kin
     uint32_t c[kBpt], sum = 0;
 #pragma unroll
     for (int j = 0; j < kBpt; ++j) { c[j] = s_cnt[kBpt * tid + j]; sum += c[j]; }
-    uint32_t incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)incl, d);
-        if (lane >= d) incl += o;
-    }
-    __syncthreads();   // s_red reuse
-    if (lane == 63) s_red[w] = incl;
-    if (tid == 0) { s_sel[0] = -1; s_sel[1] = 0; s_sel[3] = 0; }
+    const uint32_t incl = wave_incl_sum(sum);
+    if (lane == 63) s_red[32 + w] = incl;
     __syncthreads();
     uint32_t run = incl - sum;
 #pragma unroll
     for (int ww = 0; ww < NW; ++ww)
-        if (ww < w) run += s_red[ww];
+        if (ww < w) run += s_red[32 + ww];
     // b* = the bucket whose inclusive prefix first reaches kFrontK (n > kFrontK, so it exists);
     // if that would overflow the LDS room, stop one bucket earlier (possibly with nothing:
     // >= kFrontCap entries at one depth -- the clean-up kernel takes such a tile)
@@ -369,8 +416,14 @@ __device__ __forceinline__ int front_select_lds(const uint64_t *__restrict__ kin
         s_sel[2] = (int)(uint32_t)(edge > 0xffffffffull ? 0xffffffffull : edge);
         s_sel[3] = (int)(uint32_t)(first > 0xffffffffull ? 0xffffffffull : first);
     }
-    // C. select
-    for (int i0 = 0; i0 < n; i0 += kLoads * THREADS) {
+    // C. select: the keys in registers, then the remainder from memory again
+#pragma unroll
+    for (int u = 0; u < kLoads; ++u) {
+        const int b = bucket_of(kreg[u]);
+        if (u * THREADS + tid < n && b <= bstar)
+            s_out[atomicAdd(&s_cnt[b], 1u)] = kreg[u];   // s_cnt[b] becomes the END of bucket b
+    }
+    for (int i0 = kRegs; i0 < n; i0 += kLoads * THREADS) {
         uint64_t k[kLoads];
 #pragma unroll
         for (int u = 0; u < kLoads; ++u) {
@@ -381,7 +434,7 @@ __device__ __forceinline__ int front_select_lds(const uint64_t *__restrict__ kin
         for (int u = 0; u < kLoads; ++u) {
             const int b = bucket_of(k[u]);
             if (i0 + u * THREADS + tid < n && b <= bstar)
-                s_out[atomicAdd(&s_cnt[b], 1u)] = k[u];   // s_cnt[b] becomes the END of bucket b
+                s_out[atomicAdd(&s_cnt[b], 1u)] = k[u];
         }
     }
     __syncthreads();
