@@ -1,5 +1,7 @@
-"""Render a 3DGS PLY scene (the INRIA point_cloud.ply layout: mojosplat_amd/sceneio.py) on the HIP backend: load_ply ->
-evaluate_sh -> render_gaussians -> PNG (PIL if available, else .ppm).  The camera looks at the scene's centre from outside it.
+"""Render a 3DGS scene file on the HIP backend: load -> evaluate_sh -> render_gaussians -> PNG (PIL if available, else .ppm).
+The loader goes by the file: ``.splat`` -> load_splat; ``.ply`` whose header has ``element chunk`` -> load_compressed_ply (the
+PlayCanvas / SuperSplat compressed PLY: mojosplat_amd/splatio.py); any other ``.ply`` -> load_ply (the INRIA point_cloud.ply
+layout: mojosplat_amd/sceneio.py).  The camera looks at the scene's centre from outside it.
 
     python examples/render_ply.py scene.ply [--sh-degree 3] [--width 1280] [--height 720] [--distance 2.5] [--out output/render_ply.png]
 
@@ -16,8 +18,19 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mojosplat_amd import Camera, evaluate_sh, init_from_points, load_ply, look_at, render_gaussians, save_ply  # noqa: E402
+from mojosplat_amd import (Camera, evaluate_sh, init_from_points, load_compressed_ply, load_ply, load_splat, look_at,  # noqa: E402
+                           render_gaussians, save_ply)
 from render_sample import save_image  # noqa: E402
+
+
+def loader_for(path):
+    """The loader of the file's format: by extension and, for ``.ply``, by whether the header has ``element chunk``."""
+    if path.lower().endswith(".splat"):
+        return load_splat
+    with open(path, "rb") as f:
+        head = f.read(1 << 16)
+    end = head.find(b"end_header")
+    return load_compressed_ply if b"element chunk" in (head if end < 0 else head[:end]) else load_ply
 
 
 def camera_for(means3d, W, H, distance, dev):
@@ -33,7 +46,7 @@ def camera_for(means3d, W, H, distance, dev):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("ply", nargs="?", help="the scene; omit it with --demo")
+    ap.add_argument("ply", nargs="?", help="the scene (.ply, compressed .ply or .splat); omit it with --demo")
     ap.add_argument("--demo", type=int, default=0, help="write this many random Gaussians to a temporary scene and render that")
     ap.add_argument("--sh-degree", type=int, default=None)
     ap.add_argument("--width", type=int, default=1280)
@@ -56,7 +69,7 @@ def main():
         args.ply = os.path.join(tmp.name, "demo.ply")
         print(f"wrote {save_ply(args.ply, p)} bytes to {args.ply}")
     t0 = time.perf_counter()
-    p = load_ply(args.ply, device=dev)
+    p = loader_for(args.ply)(args.ply, device=dev)
     N, K = p["features"].shape[:2]
     file_degree = math.isqrt(K) - 1
     degree = file_degree if args.sh_degree is None else args.sh_degree

@@ -37,6 +37,8 @@
  *   ms_ply_pack, ms_ply_unpack        the row move between a scene's parameter tensors and the float32 rows of a 3DGS PLY
  *                                     file (nothing in the reference: it reads and writes no scene; the CUDA stack's
  *                                     save_ply / load_ply of 3DGS and gsplat's export_splats, composed from torch ops)
+ *   ms_splat_compress, _decompress,   the bit packing of the viewer formats, compressed PLY and .splat (nothing in the
+ *   ms_splat32_pack, _unpack          reference; gsplat's export_splats(format="ply_compressed" | "splat"), numpy on the host)
  *   ms_render_fwd_batch               the same for C cameras: the camera dimension of the reference's
  *                                     kernels (kernels/projection.mojo:32-37) that its wrappers pin to 1
  *
@@ -72,7 +74,7 @@ extern "C" {
 
 #define MS_ABI_VERSION 5   /* 2: ms_render_bwd takes the frame's image (render_colors); 3: ms_render_redo_counts, the band-frame pair, ms_scene_prepare;
                               4: the pose-gradient entry points (ms_pose_scratch_bytes, ms_*_pose); 5: ms_adam_step
-                              (the ms_densify_*, ms_mcmc_*, ms_knn* and ms_ply_* entry points, ms_config_fused_sort, ms_render_front_count_offset and bits 48 and 49
+                              (the ms_densify_*, ms_mcmc_*, ms_knn*, ms_ply_* and ms_splat* entry points, ms_config_fused_sort, ms_render_front_count_offset and bits 48 and 49
                               of the flag word were added under 5: new symbols and a new bit, nothing existing changed) */
 
 typedef enum ms_status {
@@ -892,6 +894,44 @@ int ms_ply_pack(int64_t N, int F, const float *const *tensors, const int32_t *wi
                 void *stream);
 int ms_ply_unpack(int64_t N, int F, int S, const float *rows, float *const *tensors, const int32_t *widths,
                   const ms_ply_column *columns, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Viewer formats: the bit packing of the PlayCanvas / SuperSplat compressed PLY and of the 32-byte .splat row
+ * (csrc/splatio.hip; both formats and the definition: mojosplat_amd/splatio.py, backend="torch").  Replaces nothing in the
+ * reference (it reads and writes no scene); the CUDA stack's gsplat export_splats(format="ply_compressed" | "splat"), which
+ * runs on the host in numpy.  One launch on `stream` per call: no host synchronisation, no allocation, no workspace, no
+ * atomics.  The kernels do only what is exact in IEEE float32 (compare, subtract, divide, multiply, add, floor, trunc,
+ * sqrt, convert; no contraction, correctly rounded division and square root): the transcendental conversions are the
+ * caller's, before ms_splat_compress / ms_splat32_pack and after the other two.  Non-finite inputs are not checked.
+ *
+ * The PREPARED arrays, rows in file order (C = ceil(N / MS_SPLAT_CHUNK) chunks; R = 3 (K - 1)):
+ *   pos   f32[N,3]  the means                       rot   f32[N,4]  the unit quaternion wxyz
+ *   lsc   f32[N,3]  log-scales clamped to [-20, 20] rgba  f32[N,4]  f_dc * SH_C0 + 0.5, then the linear opacity
+ *   shr   f32[N,R]  the higher-order SH coefficients, channel-major as f_rest_* (K == 1: ignored, may be null)
+ * and the file's elements:
+ *   chunks   f32[C,18]  min xyz, max xyz, min scale, max scale, min rgb, max rgb over the chunk's rows
+ *                       (ms_splat_decompress: f32[C, chunk_floats], chunk_floats 18, or 12 = no colour bounds: 0 and 1)
+ *   vertices u32[N,4]   packed_position (11-10-11 bits), packed_rotation (2 + 3 x 10), packed_scale, packed_color (4 x 8)
+ *   sh       u8[N,R]    a byte per higher-order coefficient (K == 1: ignored, may be null)
+ * ms_splat_compress   reads the prepared arrays, writes every element of chunks, vertices and sh: a workgroup per chunk,
+ *                     min / max by DPP steps over rows of 16 lanes and 16 x 18 LDS words.
+ * ms_splat_decompress reads the file's elements, writes every element of the prepared arrays (rot: the dropped component
+ *                     rebuilt as sqrt(max(0, 1 - a^2 - b^2 - c^2)); rgba's fourth: the opacity byte / 255).
+ * ms_splat32_pack     rows u8[N,32] = pos | scale_lin f32[N,3] (exp of the log-scales) | trunc(255 rgba) | trunc(128 rot + 128),
+ *                     bytes clamped to [0, 255]; ms_splat32_unpack is its inverse (byte / 255, (byte - 128) / 128).
+ * rot, rgba, vertices and rows are accessed 16 bytes at a time and must be 16-byte aligned; every row index is 64-bit.
+ * N = 0 is a no-op.  N < 0, a null or misaligned pointer, K outside [1, MS_SPLAT_MAX_K], chunk_floats neither 12 nor 18 ->
+ * MS_ERR_INVALID_ARG; more than (2^31 - 1) MS_SPLAT_CHUNK rows -> MS_ERR_TOO_LARGE; all before any device work.
+ * ------------------------------------------------------------------------------------- */
+#define MS_SPLAT_CHUNK 256           /* Gaussians per chunk of a compressed PLY = rows per workgroup */
+#define MS_SPLAT_MAX_K 25            /* SH coefficients per channel (degree 4) */
+int ms_splat_compress(int64_t N, int K, const float *pos, const float *rot, const float *lsc, const float *rgba,
+                      const float *shr, float *chunks, uint32_t *vertices, uint8_t *sh, void *stream);
+int ms_splat_decompress(int64_t N, int K, int chunk_floats, const float *chunks, const uint32_t *vertices, const uint8_t *sh,
+                        float *pos, float *rot, float *lsc, float *rgba, float *shr, void *stream);
+int ms_splat32_pack(int64_t N, const float *pos, const float *scale_lin, const float *rgba, const float *rot, uint8_t *rows,
+                    void *stream);
+int ms_splat32_unpack(int64_t N, const uint8_t *rows, float *pos, float *scale_lin, float *rgba, float *rot, void *stream);
 
 #ifdef __cplusplus
 }

@@ -226,6 +226,17 @@ _SIGNATURES["ms_ply_pack"] = (c_int, [c_int64, c_int, ctypes.POINTER(c_void_p), 
 _SIGNATURES["ms_ply_unpack"] = (c_int, [c_int64, c_int, c_int, c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_int),
                                         ctypes.POINTER(PlyColumn), c_void_p])
 
+SPLAT_CHUNK = 256             # MS_SPLAT_CHUNK: Gaussians per chunk of a compressed PLY = rows per workgroup
+SPLAT_MAX_K = 25
+# viewer formats (csrc/splatio.hip): N, K, [chunk_floats,] the prepared arrays and the file's elements (inputs first), stream
+_SIGNATURES["ms_splat_compress"] = (c_int, [c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p])
+_SIGNATURES["ms_splat_decompress"] = (c_int, [c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p])
+# ... and the .splat row: N, pos, scale_lin, rgba, rot, rows, stream / N, rows, pos, scale_lin, rgba, rot, stream
+_SIGNATURES["ms_splat32_pack"] = (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
+_SIGNATURES["ms_splat32_unpack"] = (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
+
 # entry points added after ABI v1's first cut; bound when present
 _OPTIONAL = {}
 

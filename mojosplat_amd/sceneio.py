@@ -45,7 +45,7 @@ type is not ``float`` / ``float32`` (both backends), a missing required property
 an element before ``vertex``, a body shorter than N rows; for backend="hip" also more than 192 float properties per vertex
 (MS_PLY_MAX_STRIDE: 64 rows of them are staged in LDS).
 
-Not covered: the ``.splat`` and compressed-PLY formats, ascii and big-endian files, non-float properties, extra per-Gaussian
+The ``.splat`` and compressed-PLY formats of the web viewers: ``splatio.py``.  Not covered: ascii and big-endian files, non-float properties, extra per-Gaussian
 tensors and optimiser moments (``torch.save(opt.state_dict())`` does the latter), float16 parameters, writing in Morton order
 (``prepare_scene`` orders a scene), the sharded trainer.
 """
