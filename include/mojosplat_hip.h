@@ -933,6 +933,41 @@ int ms_splat32_pack(int64_t N, const float *pos, const float *scale_lin, const f
                     void *stream);
 int ms_splat32_unpack(int64_t N, const uint8_t *rows, float *pos, float *scale_lin, float *rgba, float *rot, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Scene editing: a similarity transform x' = s R x + t of a whole scene -- means, log-scales, quaternions and the SH
+ * coefficients, each band l >= 1 multiplied by the rotation's (2l+1) x (2l+1) real Wigner matrix in this library's SH basis
+ * (csrc/transform.hip; the definition, and how the constants are derived: mojosplat_amd/edit.py, transform_scene with
+ * backend="torch").  Replaces nothing in the reference (it edits no scene); SuperSplat's and splat-transform's scene
+ * transforms, which run on the host.  One launch on `stream`: no host synchronisation, no allocation, no workspace, no atomics.
+ * Every operation is a separately rounded float32 multiply or add in the definition's order (no contraction, nothing skipped
+ * for a zero matrix entry): the outputs are the definition's bits.
+ *
+ *   xf : HOST, read before the call returns (it travels to the kernel by value).  All float32:
+ *        A   s R, row-major          means'  = ((A[3i] x + A[3i+1] y) + A[3i+2] z) + t[i]
+ *        t   the translation
+ *        r   R as a unit quaternion wxyz   quats' = r (x) q (Hamilton product, not normalised); a - b c is evaluated as
+ *                                          a + (-b) c, so only multiplies and adds occur
+ *        l   ln s                    scales' = scales + l
+ *        M1 .. M4  the band matrices, row-major: c'[l^2 + m] = sum_j M_l[m][j] c[l^2 + j], j ascending, per channel
+ *   K  : SH coefficients per channel, one of 1, 4, 9, 16, 25; the bands above K's degree are not read.  K = 1 copies
+ *        `features` ((N, 3) RGB features are passed as K = 1).
+ *   means, scales f32[N,3], quats f32[N,4], features f32[N,K,3]: in; out_*: the same shapes, every element written.  No output
+ *   may overlap an input.
+ * A workgroup moves MS_TRANSFORM_ROWS feature rows through LDS (K = 1: MS_TRANSFORM_ROWS_K1 rows, no LDS): 16-byte accesses on
+ * features / out_features and quats / out_quats where their base is 16-byte aligned, dwords otherwise; every row index is
+ * 64-bit.  N = 0 is a no-op.  N < 0, a K outside the set, a null or misaligned (4 bytes) pointer, a null xf ->
+ * MS_ERR_INVALID_ARG; more than (2^31 - 1) workgroups -> MS_ERR_TOO_LARGE; all before any device work.
+ * ------------------------------------------------------------------------------------- */
+#define MS_TRANSFORM_ROWS 64         /* Gaussians per workgroup, K > 1 */
+#define MS_TRANSFORM_ROWS_K1 256     /* Gaussians per workgroup, K = 1 */
+typedef struct ms_transform {
+    float A[9], t[3], r[4], l;
+    float M1[9], M2[25], M3[49], M4[81];
+} ms_transform;
+int ms_scene_transform(int64_t N, int K, const float *means, const float *scales, const float *quats, const float *features,
+                       const ms_transform *xf, float *out_means, float *out_scales, float *out_quats, float *out_features,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

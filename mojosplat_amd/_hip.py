@@ -237,6 +237,19 @@ _SIGNATURES["ms_splat_decompress"] = (c_int, [c_int64, c_int, c_int, c_void_p, c
 _SIGNATURES["ms_splat32_pack"] = (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
 _SIGNATURES["ms_splat32_unpack"] = (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
 
+
+class Transform(ctypes.Structure):
+    """ms_transform (include/mojosplat_hip.h): the float32 constants of a similarity transform, 181 floats."""
+    _fields_ = [("A", c_float * 9), ("t", c_float * 3), ("r", c_float * 4), ("l", c_float),
+                ("M1", c_float * 9), ("M2", c_float * 25), ("M3", c_float * 49), ("M4", c_float * 81)]
+
+
+TRANSFORM_ROWS = 64           # MS_TRANSFORM_ROWS: Gaussians per workgroup of ms_scene_transform, K > 1
+TRANSFORM_ROWS_K1 = 256       # MS_TRANSFORM_ROWS_K1: ... K = 1
+# scene editing (csrc/transform.hip): N, K, means, scales, quats, features, the transform (host), the four outputs, stream
+_SIGNATURES["ms_scene_transform"] = (c_int, [c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Transform),
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
+
 # entry points added after ABI v1's first cut; bound when present
 _OPTIONAL = {}
 
