@@ -21,8 +21,8 @@
 //         [sum vs, sum vs x, sum vs y, sum vs x^2, sum vs xy, sum vs y^2] = VS[entry][pixel] . MONO[pixel][6]
 //         [sum w v_r, sum w v_g, sum w v_b]                               = W[entry][pixel] . V[pixel][3]
 //     (vs = dL/dsigma of the pair, w = alpha T).  Every lane leaves vs and 255 w of eight entries in an LDS tile
-//     Y[16 rows][64 pixels], each value as TWO bf16 terms in one dword (hi = the float cut to 8 mantissa bits, lo = the
-//     exact remainder cut likewise: 16 significant bits, 2^-17 relative), and four v_mfma_f32_16x16x32_bf16 (K = 64
+//     Y[16 rows][64 pixels], each value as TWO bf16 terms in one dword (hi = the float rounded to nearest bf16, lo = the
+//     exact remainder rounded likewise: 2^-18 relative, see split_bf16), and four v_mfma_f32_16x16x32_bf16 (K = 64
 //     pixels x 2 terms, fp32 accumulation) with the per-lane constants MONO | V_hi | V_lo as the B operand turn the tile
 //     into the 8 x 9 sums.  MONO is exact in bf16 (half-integers up to 3.5 and their products); dL/dC is split like the A
 //     values.  [The first cut used v_mfma_f32_16x16x4_f32 -- exact, sixteen per tile: 307 us.  An fp32 MFMA runs at the
@@ -54,12 +54,21 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-// x as two bf16 terms, hi in the low half and lo in the high half of a dword: hi = x with its low 16 mantissa bits cut,
-// lo = (x - hi) cut likewise (x - hi is exact); hi + lo carries 16 significant bits of x
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// x as two bf16 terms, hi in the low half and lo in the high half of a dword, BOTH ROUNDED TO NEAREST: hi by an integer add
+// (half an ulp of bf16 onto the magnitude, then the cut: ties go away from zero, either sign alike), lo = x - hi (exact) by the
+// one v_cvt_pk_bf16_f32 that packs the pair (hi is a bf16 already and passes through it unchanged).  |x - hi - lo| <= 2^-18 |x|,
+// either sign; with the lo x lo product the B operand drops (<= 2^-18) a sum of products is within 3 * 2^-18 of itself.
+// [Until the needle tests (tests/test_hip_needles.py, gradients linear in alpha) both terms were CUT: up to 2^-15 off per
+// value and always towards zero, lo x lo up to 2^-14 and of the product's sign -- every sum came out short by ~3 * 2^-16 of
+// itself: 4.8e-5 and 6.1e-5 measured on colour gradients of a few pixels.  Rounding costs one instruction more per value:
+// backward 250 -> 254 us at config 3 in interleaved runs; both hi and lo through the conversion instruction: 256.]
 __device__ __forceinline__ unsigned split_bf16(float x) {
-    const unsigned xb = __float_as_uint(x);
-    const float lo = x - __uint_as_float(xb & 0xffff0000u);
-    return __builtin_amdgcn_perm(__float_as_uint(lo), xb, 0x07060302u);
+    const float hi = __uint_as_float((__float_as_uint(x) + 0x8000u) & 0xffff0000u);
+    const f32x2 p = {hi, x - hi};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(p, bf16x2));
 }
 
 struct BwdQArgs {
@@ -170,9 +179,9 @@ __device__ __forceinline__ void bwd_quad(const BwdQArgs &A, const int tile, cons
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const float c = vo[k] * ms::kInv255;
-            const unsigned c_hi = __float_as_uint(c) & 0xffff0000u;
-            tab[(6 + k) * kYStride + lane] = (c_hi >> 16) | c_hi;                                     // hi(dL/dC) for both terms
-            tab[(9 + k) * kYStride + lane] = __float_as_uint(c - __uint_as_float(c_hi)) >> 16;       // lo(dL/dC) for the hi term
+            const unsigned s = split_bf16(c);                                                        // hi | lo << 16, both rounded to nearest
+            tab[(6 + k) * kYStride + lane] = (s & 0xffffu) | (s << 16);                              // hi(dL/dC) for both terms
+            tab[(9 + k) * kYStride + lane] = s >> 16;                                                // lo(dL/dC) for the hi term
         }
         tab[12 * kYStride + lane] = 0u;
         wave_lds_sync_q();

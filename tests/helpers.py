@@ -138,7 +138,7 @@ def check_image_strict(img, ref, margin, *, tag, atol=1e-4, eps=1e-5, flip_cap=1
 # Two bars per tensor.  (1) max norm: |g - g_ref| <= rel * max|g_ref| -- what rounds 1-4 asserted; it is blind to the error
 # of the small-gradient majority.  (2) per element: every element with |g_ref| >= floor * max|g_ref| must agree to
 # elem_rel RELATIVE to itself (and the 99.9th percentile of those errors to elem_p999).  The backward rasteriser's
-# two-term bf16 tile (2^-17 per term) and its approximate reciprocal are what bar (2) watches.
+# two-term bf16 tile (both terms rounded to nearest: 2^-18 per value) and its approximate reciprocal are what bar (2) watches.
 # Where the bars sit (measured, profiles/r05_grad_stats.txt): against float64 autograd the worst element of any test is
 # 3.4e-4 off -> 2e-3 on EVERY element.  Fused against the per-stage functions BOTH sides are fp32 with different orders of
 # summation (the per-stage kernel walks back to front and recovers T by division): regular scenes up to 3e-3 on a single
