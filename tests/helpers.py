@@ -210,6 +210,13 @@ def general_camera(W, H, fx, fy, cx, cy, *, near=0.5, far=30.0, eye=(1.8, -1.2, 
                   cx=cx, cy=cy, near=near, far=far)
 
 
+def _posed(cam):
+    """The same camera with a view matrix of its own that requires grad (the camera pose as a leaf)."""
+    vm = cam.view_matrix.detach().clone().requires_grad_(True)
+    return Camera(R=cam.R, T=cam.T, H=cam.H, W=cam.W, fx=cam.fx, fy=cam.fy, cx=cam.cx, cy=cam.cy, near=cam.near,
+                  far=cam.far, view_matrix=vm)
+
+
 # name -> (W, H, fx, fy, cx, cy, near, far, axes whose principal point is off-centre)
 GENERAL_CAMERAS = {
     "fx>fy_pp_xy": (330, 190, 300.0, 240.0, 0.35 * 330, 0.62 * 190, 0.5, 30.0, "xy"),

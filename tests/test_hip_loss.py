@@ -10,12 +10,11 @@ import pytest
 import torch
 
 import mojosplat_amd as ms
-from helpers import GOLDEN_DIR, assert_grad_close, camera_from_golden, load_golden
+from helpers import GOLDEN_DIR, _posed, assert_grad_close, camera_from_golden, load_golden
 from mojosplat_amd import _hip, photometric_loss
 from mojosplat_amd.autograd import render_gaussians_trainable
 from mojosplat_amd.densify import DensifyStats
 from mojosplat_amd.loss import photometric_loss_torch
-from mojosplat_amd.utils import Camera
 
 pytestmark = pytest.mark.gpu
 
@@ -216,12 +215,6 @@ def test_layouts_give_the_same_numbers(device):
         photometric_loss(xg, y.to(device).requires_grad_(True))
     with pytest.raises(_hip.HipBackendError, match="channels"):
         photometric_loss(torch.rand(8, 8, 5, device=device), torch.rand(8, 8, 5, device=device))
-
-
-def _posed(cam):
-    vm = cam.view_matrix.detach().clone().requires_grad_(True)
-    return Camera(R=cam.R, T=cam.T, H=cam.H, W=cam.W, fx=cam.fx, fy=cam.fy, cx=cam.cx, cy=cam.cy, near=cam.near,
-                  far=cam.far, view_matrix=vm)
 
 
 def _step(sc, cam, target, backend, bg):
