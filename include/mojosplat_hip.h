@@ -39,6 +39,8 @@
  *                                     save_ply / load_ply of 3DGS and gsplat's export_splats, composed from torch ops)
  *   ms_splat_compress, _decompress,   the bit packing of the viewer formats, compressed PLY and .splat (nothing in the
  *   ms_splat32_pack, _unpack          reference; gsplat's export_splats(format="ply_compressed" | "splat"), numpy on the host)
+ *   ms_bilagrid_slice_*,              bilateral-grid colour correction between the render and the loss, and the grids'
+ *   ms_bilagrid_tv_*                  total-variation loss (nothing in the reference; gsplat's use_bilateral_grid / lib_bilagrid)
  *   ms_render_fwd_batch               the same for C cameras: the camera dimension of the reference's
  *                                     kernels (kernels/projection.mojo:32-37) that its wrappers pin to 1
  *
@@ -967,6 +969,49 @@ typedef struct ms_transform {
 int ms_scene_transform(int64_t N, int K, const float *means, const float *scales, const float *quats, const float *features,
                        const ms_transform *xf, float *out_means, float *out_scales, float *out_quats, float *out_features,
                        void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Bilateral-grid colour correction (csrc/bilagrid.hip; the definitions: mojosplat_amd/bilagrid.py, bilagrid_slice_torch and
+ * bilagrid_tv_loss_torch).  Nothing in the reference; gsplat's use_bilateral_grid, and with L = Gh = Gw = 1 the per-image
+ * 3x4 exposure matrix of 3DGS.
+ *   grids  : f32[B,12,L,Gh,Gw] (gsplat's layout); coefficient c = 4 i + j is entry (i, j) of the 3x4 matrix, j = 3 the offset.
+ *   img    : f32[B,H,W,3], channel innermost -- the tensor ms_render_fwd writes; image b goes through grid b.
+ *   out    : f32[B,H,W,3], overwritten: out_i = sum_j A[4 i + j] rgb_j + A[4 i + 3], A interpolated trilinearly at
+ *            u = (x + 0.5) / W (Gw - 1), v = (y + 0.5) / H (Gh - 1), z = ((0.299 r + 0.587 g) + 0.114 b) (L - 1) -- products and
+ *            sums rounded separately; per axis of size n: vertex 0 if n == 1, else tc = clamp(t, 0, n - 1),
+ *            i0 = min(floor(tc), n - 2), weights (1 - (tc - i0), tc - i0) on (i0, i0 + 1).
+ *   v_out  : f32[B,H,W,3] = dL/dout.
+ *   v_grids: f32[B,12,L,Gh,Gw] = dL/dgrids, EVERY element overwritten (exact zeros where no pixel reaches), or NULL.
+ *   v_img  : f32[B,H,W,3] = dL/dimg, overwritten, or NULL: A^T v_out, plus -- where 0 < z < L - 1 only -- the term through
+ *            the guidance, (L - 1) dA/df_z . (v_out x (rgb, 1)) times (0.299, 0.587, 0.114).  Nothing flows into u and v.
+ *   workspace: ms_bilagrid_slice_workspace_bytes(B, H, W, L, Gh, Gw) bytes (0: bad sizes), needed with v_grids only: the
+ *            partial sums [b][vertex][chunk of 32 pixel rows][level][12] of the vertex-centred gather.
+ * One launch forward; backward one launch for v_img and two for v_grids; on `stream`, no host synchronisation, no
+ * allocation, no float atomics: the same inputs give the same bits on every run.  Pixel offsets are 64-bit.
+ *
+ * ms_bilagrid_tv_*: gsplat's total_variation_loss -- per grid axis of size n >= 2 the sum of squared differences of
+ * neighbours along it over their number in one batch entry (12 x the other two sizes x (n - 1)), the three added, over B; an
+ * axis of size 1 contributes 0.
+ *   workspace: ms_bilagrid_tv_workspace_bytes(B, L, Gh, Gw) bytes (0: bad sizes): per-workgroup partial sums.
+ *   out1   : f32[1] (DEVICE), overwritten.     v_loss : f32[1] (DEVICE), read by the kernel.
+ *   v_grids: f32[B,12,L,Gh,Gw] = v_loss * d tv / d grids, overwritten.
+ * Two launches forward (partial sums, then one workgroup adding them in a fixed order in double), one backward; 16-byte
+ * accesses along Gw where Gw is a multiple of 4 and the bases are 16-byte aligned, dwords otherwise.
+ *
+ * Sizes <= 0 or a null pointer (v_grids / v_img excepted; a workspace goes with v_grids) -> MS_ERR_INVALID_ARG; a short
+ * workspace -> MS_ERR_WORKSPACE; grids of more than 2^31 - 1 elements, an image side above 2^23, more than 65535 tile rows
+ * (16 pixels), images, or row chunks of a vertex -> MS_ERR_TOO_LARGE; all before any device work.
+ * ------------------------------------------------------------------------------------- */
+size_t ms_bilagrid_slice_workspace_bytes(int B, int H, int W, int L, int Gh, int Gw);
+int ms_bilagrid_slice_fwd(int B, int H, int W, int L, int Gh, int Gw, const float *grids, const float *img, float *out,
+                          void *stream);
+int ms_bilagrid_slice_bwd(int B, int H, int W, int L, int Gh, int Gw, const float *grids, const float *img,
+                          const float *v_out, void *workspace, size_t workspace_bytes, float *v_grids, float *v_img,
+                          void *stream);
+size_t ms_bilagrid_tv_workspace_bytes(int B, int L, int Gh, int Gw);
+int ms_bilagrid_tv_fwd(int B, int L, int Gh, int Gw, const float *grids, void *workspace, size_t workspace_bytes,
+                       float *out1, void *stream);
+int ms_bilagrid_tv_bwd(int B, int L, int Gh, int Gw, const float *grids, const float *v_loss, float *v_grids, void *stream);
 
 #ifdef __cplusplus
 }

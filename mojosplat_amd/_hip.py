@@ -250,6 +250,15 @@ TRANSFORM_ROWS_K1 = 256       # MS_TRANSFORM_ROWS_K1: ... K = 1
 _SIGNATURES["ms_scene_transform"] = (c_int, [c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Transform),
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
 
+# bilateral-grid colour correction (csrc/bilagrid.hip): B, H, W, L, Gh, Gw, grids, img, ... / B, L, Gh, Gw, grids, ...
+_SIGNATURES["ms_bilagrid_slice_workspace_bytes"] = (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int])
+_SIGNATURES["ms_bilagrid_slice_fwd"] = (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p])
+_SIGNATURES["ms_bilagrid_slice_bwd"] = (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_size_t, c_void_p, c_void_p, c_void_p])
+_SIGNATURES["ms_bilagrid_tv_workspace_bytes"] = (c_size_t, [c_int, c_int, c_int, c_int])
+_SIGNATURES["ms_bilagrid_tv_fwd"] = (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p])
+_SIGNATURES["ms_bilagrid_tv_bwd"] = (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p])
+
 # entry points added after ABI v1's first cut; bound when present
 _OPTIONAL = {}
 
