@@ -41,6 +41,9 @@
  *   ms_splat32_pack, _unpack          reference; gsplat's export_splats(format="ply_compressed" | "splat"), numpy on the host)
  *   ms_bilagrid_slice_*,              bilateral-grid colour correction between the render and the loss, and the grids'
  *   ms_bilagrid_tv_*                  total-variation loss (nothing in the reference; gsplat's use_bilateral_grid / lib_bilagrid)
+ *   ms_contrib_accumulate             per-Gaussian contribution statistics of a view (blended pixels, largest and summed blend
+ *                                     weight, the sum under a pixel weight map), for pruning before export and for lifting
+ *                                     image masks to Gaussians (nothing in the reference; RadSplat's and LightGaussian's scores)
  *   ms_render_fwd_batch               the same for C cameras: the camera dimension of the reference's
  *                                     kernels (kernels/projection.mojo:32-37) that its wrappers pin to 1
  *
@@ -1012,6 +1015,37 @@ size_t ms_bilagrid_tv_workspace_bytes(int B, int L, int Gh, int Gw);
 int ms_bilagrid_tv_fwd(int B, int L, int Gh, int Gw, const float *grids, void *workspace, size_t workspace_bytes,
                        float *out1, void *stream);
 int ms_bilagrid_tv_bwd(int B, int L, int Gh, int Gw, const float *grids, const float *v_loss, float *v_grids, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Per-Gaussian contribution statistics of one view (csrc/contrib.hip; the definition: mojosplat_amd/contrib.py,
+ * contributions_from_lists_torch).  Nothing in the reference; the scores that RadSplat (max blend weight over the training
+ * rays) and LightGaussian (summed blend weight) prune by, and the sum that lifts an image mask to Gaussians.
+ * Every pixel walks its tile's list front to back with ms_rasterize_to_pixels_3dgs_fwd's rules: sigma = 0.5 (a dx^2 + c dy^2)
+ * + b dx dy at the pixel centre, alpha = min(0.999, o exp(-sigma)); an entry is skipped when sigma < 0 or alpha < 1/255; the
+ * pixel stops BEFORE adding an entry when T (1 - alpha) <= 1e-4.  An entry that is added is blended, with w = alpha T_before.
+ *   means2d f32[N,2], conics f32[N,3], opacities f32[N] (activated), tile_ranges i32[th,tw,2], flatten_ids i32[M]: the
+ *            per-stage lists (ms_project_gaussians_fwd, ms_isect_tiles_*), tile_size 16 or 32, th = ceil(H / tile_size).
+ *            A range is clamped to [0, M]; an id outside [0, N) blends nothing.
+ *   weights: f32[H,W] or NULL; read clamped to [0, 1], NaN as 0.
+ *   pixels : i64[N], += the number of pixels that blended the Gaussian.
+ *   max_weight: f32[N], = max(itself, the largest w); updated as a 32-bit unsigned maximum on the bit pattern, so it must
+ *            hold non-negative floats (zeros at first).
+ *   sum_q  : i64[N], += sum w in units of 2^-30 (MS_CONTRIB_FIXED_ONE): the float32 partial sum of a (16x16 pixel block,
+ *            Gaussian) -- a wave's 64 pixels in pixel order, the four waves in order -- is rounded to the nearest unit
+ *            (ties to even) and added as an integer, so the result does not depend on the order of workgroups or calls.
+ *   wsum_q : i64[N] or NULL with weights == NULL (then untouched), += the same sum with every term times its pixel's weight.
+ * One launch on `stream`: a workgroup per 16x16 pixel block (a 32-pixel tile is walked by four), entries staged through LDS
+ * 64 at a time (a wave walks only those that can reach its pixels: a conservative test, the result is that of walking all), the reduction over pixels through LDS in a fixed order; the only traffic between workgroups is integer
+ * atomics (64-bit add, 32-bit unsigned max), none for a (block, Gaussian) that blended no pixel.  No workspace, no host
+ * synchronisation, bitwise reproducible.  Bytes: 4 + 24 per list entry read (per block), up to four atomics per blended
+ * (block, entry).  N == 0 or M == 0 returns at once, buffers untouched.
+ * Sizes < 0, W or H <= 0, another tile_size, a null or misaligned pointer -> MS_ERR_INVALID_ARG; N or M above 2^31 - 1 or more
+ * pixel blocks than a launch has workgroups -> MS_ERR_TOO_LARGE; all before any device work.
+ * ------------------------------------------------------------------------------------- */
+#define MS_CONTRIB_FIXED_ONE 1073741824 /* 2^30 */
+int ms_contrib_accumulate(int64_t N, int64_t M, const float *means2d, const float *conics, const float *opacities,
+                          const int32_t *tile_ranges, const int32_t *flatten_ids, const float *weights, int W, int H,
+                          int tile_size, int64_t *pixels, float *max_weight, int64_t *sum_q, int64_t *wsum_q, void *stream);
 
 #ifdef __cplusplus
 }

@@ -21,6 +21,8 @@ from .sceneio import save_ply, load_ply, pack_ply_rows, unpack_ply_rows, ply_hea
 from .splatio import (compress_scene, decompress_scene, save_compressed_ply, load_compressed_ply, save_splat, load_splat,
                       CompressedScene)
 from .bilagrid import bilagrid_identity, bilagrid_slice, bilagrid_tv_loss, bilagrid_slice_torch, bilagrid_tv_loss_torch
+from .contrib import (ContributionStats, contributions_from_lists, accumulate_contributions, select_by_contribution, lift_mask,
+                      prune_scene)
 from .edit import sh_rotation_matrices, transform_scene, transform_camera, crop_scene, merge_scenes
 
 
@@ -36,4 +38,4 @@ def release_scratch():
     _release()
 
 __all__ = ["Camera", "look_at", "project_gaussians", "bin_gaussians_to_tiles",
-           "rasterize_gaussians", "render_gaussians", "render_gaussians_batch", "evaluate_sh", "DensifyStats", "photometric_loss", "ssim", "GaussianAdam", "densify_and_prune", "reset_opacities", "DensifyResult", "relocate_dead", "grow", "inject_noise", "McmcResult", "knn", "init_from_points", "scene_extent", "save_ply", "load_ply", "pack_ply_rows", "unpack_ply_rows", "ply_header", "parse_ply_header", "PlyLayout", "compress_scene", "decompress_scene", "save_compressed_ply", "load_compressed_ply", "save_splat", "load_splat", "CompressedScene", "sh_rotation_matrices", "transform_scene", "transform_camera", "crop_scene", "merge_scenes", "bilagrid_identity", "bilagrid_slice", "bilagrid_tv_loss", "bilagrid_slice_torch", "bilagrid_tv_loss_torch", "release_scratch", "prepare_scene", "TILE_SIZE"]
+           "rasterize_gaussians", "render_gaussians", "render_gaussians_batch", "evaluate_sh", "DensifyStats", "photometric_loss", "ssim", "GaussianAdam", "densify_and_prune", "reset_opacities", "DensifyResult", "relocate_dead", "grow", "inject_noise", "McmcResult", "knn", "init_from_points", "scene_extent", "save_ply", "load_ply", "pack_ply_rows", "unpack_ply_rows", "ply_header", "parse_ply_header", "PlyLayout", "compress_scene", "decompress_scene", "save_compressed_ply", "load_compressed_ply", "save_splat", "load_splat", "CompressedScene", "sh_rotation_matrices", "transform_scene", "transform_camera", "crop_scene", "merge_scenes", "bilagrid_identity", "bilagrid_slice", "bilagrid_tv_loss", "bilagrid_slice_torch", "bilagrid_tv_loss_torch", "ContributionStats", "contributions_from_lists", "accumulate_contributions", "select_by_contribution", "lift_mask", "prune_scene", "release_scratch", "prepare_scene", "TILE_SIZE"]

@@ -259,6 +259,12 @@ _SIGNATURES["ms_bilagrid_tv_workspace_bytes"] = (c_size_t, [c_int, c_int, c_int,
 _SIGNATURES["ms_bilagrid_tv_fwd"] = (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p])
 _SIGNATURES["ms_bilagrid_tv_bwd"] = (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p])
 
+# contribution statistics (csrc/contrib.hip): N, M, means2d, conics, opacities, tile_ranges, ids, weights or None, W, H,
+# tile_size, pixels, max_weight, sum_q, wsum_q or None, stream
+CONTRIB_FIXED_ONE = 1 << 30   # MS_CONTRIB_FIXED_ONE: units of the fixed-point sums
+_SIGNATURES["ms_contrib_accumulate"] = (c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                                c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
+
 # entry points added after ABI v1's first cut; bound when present
 _OPTIONAL = {}
 

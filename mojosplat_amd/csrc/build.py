@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["api.hip", "project.hip", "binning.hip", "rasterize.hip", "rasterize_bwd.hip", "rasterize_bwdq.hip",
            "project_bwd.hip", "pipeline.hip", "sh.hip", "loss.hip", "adam.hip", "densify.hip", "mcmc.hip", "knn.hip",
-           "sceneio.hip", "splatio.hip", "transform.hip", "bilagrid.hip"]
+           "sceneio.hip", "splatio.hip", "transform.hip", "bilagrid.hip", "contrib.hip"]
 # per-source flags.  rasterize.hip: fp32 denormals flushed -- its blend loop selects by underflow
 # (ms::kFlushK in ms_common.hpp; scripts/ubench/flush_select.hip)
 SOURCE_FLAGS = {"rasterize.hip": ["-fgpu-flush-denormals-to-zero"], "rasterize_bwdq.hip": ["-fgpu-flush-denormals-to-zero"]}
